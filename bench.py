@@ -6,7 +6,11 @@ V views (one step of the trange at /root/reference/PMVO.py:572-574): the H2D upl
 visibility / tap lists (mh_project_taps_kernel), base-view ranking (mh_topk_kernel) and the fused loss search
 (mh_search3_kernel), maps resident in HBM, no file IO.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed region, what the last timed step returned (points, line_ori, min_loss, high_conf; rank
+0's chunk at N > 1) is written as DIR/<name>.npy in float32; the inputs depend on the arguments only, so two builds can be
+compared output for output.
 
 N > 1: one process per GPU over RCCL.  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks are
 already there (RANK / LOCAL_RANK / WORLD_SIZE); started plainly, `python bench.py --gpus N` launches the N ranks
@@ -61,6 +65,8 @@ def parse():
     ap.add_argument("--topk-order", type=int, default=-1, help="0 torch.topk's tie order (default), 1 index order (A/B)")
     ap.add_argument("--streams", type=int, default=3,
                     help="HIP streams the independent iterations alternate on (as monohair_amd.pmvo.optimize does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
@@ -96,6 +102,24 @@ class Emitter:
                 return
             self.done = True
             print(json.dumps(out), flush=True)
+
+
+DUMP_NAMES = ("points", "line_ori", "min_loss", "high_conf")      # forward()'s four results, in order
+
+
+def dump_outputs(d, result):
+    """--dump-outputs: the four device tensors forward() returned in the last timed step (the uploaded chunk [N,3], line
+    orientation [N,3], minimal loss [N], high-confidence flag [N]) as d/<name>.npy, all float32 (the flag as 0 / 1).  N is at
+    most CHUNK, so the files stay far below 64 MB.  Called after the timed region's closing barrier: the step is complete."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    shapes = {}
+    for name, t in zip(DUMP_NAMES, result):
+        arr = t.detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(d, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return {"dir": d, "dtype": "float32", "shapes": shapes}
 
 
 def main():
@@ -260,6 +284,7 @@ def main():
                       file=sys.stderr)
             prev = t
     last_chunk = my[(a.warmup + a.steps - 1) % len(my)]
+    dumped = dump_outputs(a.dump_outputs, last) if a.dump_outputs and rank == 0 else None
     timed_region_s = dt
     per_rank = [a.steps / dt]
     if dist is not None:
@@ -310,6 +335,8 @@ def main():
             "step_input": "host numpy chunk [5000,3] float64, uploaded inside the step (PMVO.py:40); maps resident in HBM",
         },
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     em = Emitter()
 
     # --- legs that need every rank: the RCCL volume reduce and the sharded full pass (N > 1).  A watchdog prints the

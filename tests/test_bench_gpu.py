@@ -59,6 +59,25 @@ def test_line_verifies_its_own_outputs_against_the_oracle():
     assert rf["traffic"] is None or "profiles/traffic.json" in rf["traffic_source"]
 
 
+def test_dump_outputs_are_the_last_steps_results_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: forward()'s four results of the last timed step as float32 .npy files; two runs with the same
+    arguments write the same bits (the inputs depend on the arguments only)"""
+    import numpy as np
+
+    runs = []
+    for tag in ("a", "b"):
+        d = run_bench(SMALL + ["--no-secondary", "--dump-outputs", str(tmp_path / tag)])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dump_outputs"]["dtype"] == "float32"
+        runs.append({n: np.load(tmp_path / tag / (n + ".npy")) for n in ("points", "line_ori", "min_loss", "high_conf")})
+    a, b = runs
+    n = a["points"].shape[0]
+    assert 0 < n <= 5000 and a["points"].shape == a["line_ori"].shape == (n, 3)
+    assert a["min_loss"].shape == a["high_conf"].shape == (n,) and set(np.unique(a["high_conf"])) <= {0.0, 1.0}
+    assert np.isfinite(a["min_loss"]).any()
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k], equal_nan=True), k
+
+
 def test_gpus_2_spawns_two_ranks_itself():
     d = run_bench(["--gpus", "2"] + SMALL_CPU, env={"MH_DIST_BACKEND": "gloo", "MH_DEVICE_OVERRIDE": "0"})
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["backend"] == "gloo"
