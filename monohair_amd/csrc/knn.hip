@@ -56,10 +56,20 @@ __global__ __launch_bounds__(128) void mh_knn_kernel(MhGrid g, const float *__re
         const float *__restrict__ q = reinterpret_cast<const float *>(queries);
         dqx = (double)q[3 * qi], dqy = (double)q[3 * qi + 1], dqz = (double)q[3 * qi + 2];
     }
-    const float qx = (float)dqx, qy = (float)dqy, qz = (float)dqz;
-    const int cx = min(max((int)floorf((qx - g.ox) / g.h), 0), g.dx - 1);
-    const int cy = min(max((int)floorf((qy - g.oy) / g.h), 0), g.dy - 1);
-    const int cz = min(max((int)floorf((qz - g.oz) / g.h), 0), g.dz - 1);
+    // the cell of the query: a float32 query by the formula of the data points' cells (mh_cell_key_kernel), a float64
+    // one from its exact coordinates -- rounding it to float32 first moves it by up to half an ulp of its magnitude, which
+    // is more than the reach margin below once the cells are small against the coordinates (1 km / 0.1 mm cells).  The
+    // clamp to the grid happens in floating point, so a query far outside never converts an out-of-range value to int.
+    int cx, cy, cz;
+    if (q64) {
+        cx = (int)fmin(fmax(floor((dqx - (double)g.ox) / (double)g.h), 0.0), (double)(g.dx - 1));
+        cy = (int)fmin(fmax(floor((dqy - (double)g.oy) / (double)g.h), 0.0), (double)(g.dy - 1));
+        cz = (int)fmin(fmax(floor((dqz - (double)g.oz) / (double)g.h), 0.0), (double)(g.dz - 1));
+    } else {
+        cx = (int)fminf(fmaxf(floorf(((float)dqx - g.ox) / g.h), 0.0f), (float)(g.dx - 1));
+        cy = (int)fminf(fmaxf(floorf(((float)dqy - g.oy) / g.h), 0.0f), (float)(g.dy - 1));
+        cz = (int)fminf(fmaxf(floorf(((float)dqz - g.oz) / g.h), 0.0f), (float)(g.dz - 1));
+    }
     int st = 1;   // 1: ring limit reached (cells too small for this query), 2: candidate buffer overflow (too large)
     for (int ring = max(ring0, 1); ring <= MH_KNN_MAXRING; ++ring) {
         int cnt = 0;
@@ -67,7 +77,7 @@ __global__ __launch_bounds__(128) void mh_knn_kernel(MhGrid g, const float *__re
         const bool whole_grid = (cx - ring <= 0) && (cy - ring <= 0) && (cz - ring <= 0) && (cx + ring >= g.dx - 1) &&
                                 (cy + ring >= g.dy - 1) && (cz + ring >= g.dz - 1);
         // the block reaches at least `ring` cells beyond the query's cell; 1e-3 of a cell absorbs the float rounding of
-        // the cell indices of the query and of the points (coordinates / h < 2^10, i.e. errors below 1e-4 cells)
+        // the cell indices of the query and of the points ((coordinate - origin) / h < 2^10, i.e. errors below 1e-4 cells)
         const double reach = ((double)ring - 1.0e-3) * (double)g.h;
         const double reach2 = whole_grid ? __builtin_inf() : reach * reach;
         const int x0 = max(cx - ring, 0), x1 = min(cx + ring, g.dx - 1);

@@ -306,6 +306,7 @@ class GridKNN:
         # cell size of it, so the first ring answers almost every query and only the points within that reach get sorted
         self.h = max(rk * 1.2, ext / 480.0)
         self.last_retries = 0
+        self.last_exhaustive = 0
 
     def _geometry(self, h):
         origin = self._lo.astype(np.float32)
@@ -380,9 +381,9 @@ class GridKNN:
     def query_nosync(self, queries, k, valid_dev=None, self_query=False):
         """The first attempt of query() only, nothing read back: -> (index [Q,k] int32, status [Q] int32) on the device.
         status != 0 marks queries that need query()'s retries on another cell size (their rows of the index are zeros).
-        With valid_dev (uint8 [M] on the device) the caller guarantees that at least k points are flagged (fewer: the kernel
-        pads with -1, which is not an index).  refine's device-resident pass checks the status once it has synchronised
-        anyway and falls back to query() if any is set."""
+        With valid_dev (uint8 [M] on the device) only the flagged points are neighbours; with fewer than k of them a row ends
+        in -1 (not an index), after finish_nosync too.  refine's device-resident pass checks the status once it has synchronised
+        anyway and hands the rows that need it to finish_nosync."""
         q = self._queries(queries)
         perm = self._grid(self.h)[3] if (self_query and q.shape[0] == self.M) else None
         return self._run(self.h, q, min(int(k), self.M), perm, valid_dev, zero=True)
@@ -406,17 +407,23 @@ class GridKNN:
                 self.last_retries += 1
         # extreme density contrast (a sparse query whose k-ball swallows a dense cluster) defeats every cell size:
         # those few queries are answered by exhaustive search, also on the GPU (same fp64 distances, stable sort =
-        # ties by index)
+        # ties by index; with fewer than k valid points the row ends in -1, as the kernel pads it)
         left = np.flatnonzero(st != 0)
         self.last_exhaustive = int(left.size)
         if left.size:
             p64 = self._raw.to(torch.float64)
+            if valid is not None:
+                vb = valid.bool()
+                nv = int(vb.sum())
             for i in left.tolist():
                 d = p64 - q[i].to(torch.float64)
                 d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
                 if valid is not None:
-                    d2 = torch.where(valid.bool(), d2, torch.full_like(d2, float("inf")))
-                out[i] = torch.sort(d2, stable=True).indices[:k].to(torch.int32)
+                    d2 = torch.where(vb, d2, torch.full_like(d2, float("inf")))
+                row = torch.sort(d2, stable=True).indices[:k].to(torch.int32)
+                if valid is not None and nv < k:
+                    row[nv:] = -1
+                out[i] = row
 
     def finish_nosync(self, queries, k, out, status_host, valid_dev=None):
         """query()'s retries for the rows a query_nosync left unfinished (status_host != 0), in place in `out`."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Randomised sweeps of the other kernels against their checkers (GPU box):
-  k-NN grid search vs scipy.spatial.KDTree, depth rasteriser / Gabor bank (all variants) / medoid / voxel fit vs the
+  k-NN grid search (float32 / float64 queries, with and without a validity mask) vs the fp64 brute force, depth rasteriser / Gabor bank (all variants) / medoid / voxel fit vs the
   CPU oracle.  Every comparison is for exact equality.
     python tests/stress_more.py --minutes 5 [--seed 0]
 """
@@ -11,7 +11,6 @@ import time
 
 import numpy as np
 import torch
-from scipy.spatial import KDTree
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,6 +21,7 @@ from monohair_amd.gabor import calOrientationGabor, gabor_bank  # noqa: E402
 from monohair_amd.pmvo_utils import GridKNN, compute_points_similarity, voxel_fit  # noqa: E402
 from monohair_amd import _lib  # noqa: E402
 from monohair_amd.render import DepthRenderer, StrandRenderer, strand_line_buffers  # noqa: E402
+from test_knn_paths_gpu import brute_knn  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--minutes", type=float, default=3.0)
@@ -55,14 +55,16 @@ while time.time() < t_end:
     k = int(rng.choice([1, 7, 32, 100]))
     q = np.concatenate([pts[rng.choice(n, min(n, 300), replace=False)],
                         (pts[:100] + rng.normal(0, 0.01, (min(n, 100), 3))).astype(np.float32)])
-    got = GridKNN(pts, k_hint=k, device=DEV).query(q, k).cpu().numpy()
-    kk = min(k, n)
-    d, ref = KDTree(data=pts).query(q, kk)
-    ref = np.asarray(ref).reshape(len(q), kk)
+    if rng.random() < 0.5:                                            # float64 queries keep their exact coordinates
+        q = q.astype(np.float64) + rng.normal(0, 1e-9, q.shape)
+    valid = rng.random(n) < rng.uniform(0.05, 1.0) if rng.random() < 0.5 else None
+    if valid is not None and not valid.any():
+        valid = None
+    got = GridKNN(pts, k_hint=k, device=DEV).query(q, k, valid=valid).cpu().numpy()
+    # the fp64 (d2, index) brute force: exact index equality, ties included (scipy's KDTree breaks ties in another order)
+    ref, _ = brute_knn(pts, q, min(k, n if valid is None else int(valid.sum())), valid)
     if not np.array_equal(got, ref):
-        dg = np.linalg.norm(pts[got].astype(np.float64) - q[:, None].astype(np.float64), axis=-1)
-        if not np.allclose(dg, np.asarray(d).reshape(len(q), kk), rtol=0, atol=0):    # only exact distance ties may differ
-            bad.append(("knn", n, k))
+        bad.append(("knn", n, k, q.dtype.name, valid is not None))
     count["knn"] += 1
     # ---- rasteriser
     H, W = int(rng.integers(20, 300)), int(rng.integers(20, 300))

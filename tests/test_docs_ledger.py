@@ -50,3 +50,15 @@ def test_every_tolerance_the_ledger_quotes_is_one_a_test_still_applies():
     # bars of earlier rounds that plain equality has replaced
     for stale in ("N mod 64", "vs the DOUBLED batch", "exact vs the doubled batch", "exact vs the recomposed batch"):
         assert stale not in text, "ledger still carries the round-4 statement %r" % stale
+
+
+def test_every_test_node_the_ledger_names_exists():
+    """citations of the form `tests/<file>.py::<test>`: the file exists and defines that test (not some other file)"""
+    text = open(LEDGER).read()
+    nodes = set(re.findall(r"`tests/(test_[A-Za-z0-9_]+\.py)::(test_[A-Za-z0-9_]+)`", text))
+    assert nodes, "the ledger names no test nodes?"
+    for f, name in sorted(nodes):
+        path = os.path.join(ROOT, "tests", f)
+        assert os.path.exists(path), "ledger cites tests/%s: no such file" % f
+        assert re.search(r"^def %s\(" % re.escape(name), open(path).read(), re.M), \
+            "ledger cites tests/%s::%s: no test of that name in that file" % (f, name)
