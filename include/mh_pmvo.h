@@ -375,6 +375,39 @@ int mh_strands_accept(int W, int H, int Z, float *flag, const float *pts, const 
  * of len (device, int64).  mh_strands_accept reads the packed list with stride 0 and first = offsets. */
 int mh_strands_compact(mh_ctx *ctx, const float *rows, const int32_t *first, const int32_t *len, const long long *offsets,
                        int n, int stride, float *packed, void *stream);
+/* Segment connection (HairGrowing.find_connect_info, HairGrow.py:434-590 with connect_segments :303-420) and the Laplacian
+ * smoothing of Utils/Utils.py:1148-1198, all float64.  Strands are one point list pts [P,3] with offsets [n+1] (int64),
+ * every pointer on the device.
+ * mh_end_knn64: KDTree(data).query(q, k=50, distance_upper_bound=bound) per query, pruned to d^2 < bound^2 and sorted by
+ *   (distance, index); with skip_self the query's own index is dropped afterwards.  data is binned on a uniform grid of
+ *   gx*gy*gz cells no smaller than `bound` (order = data indices sorted by cell, cstart [cells+1]); qcell [nq,3] = each
+ *   query's cell by the same formula.  Rows of 50: out_idx / out_dist (the distance itself) [nq,50], out_cnt [nq].
+ * mh_connect_candidates: find_best_connect_strands for both ends of every segment.  nei_* (host arrays of 4 device
+ *   pointers): the lists root->roots, root->tips, tip->roots, tip->tips of mh_end_knn64.  best[2i+e] = the segment joined
+ *   at end e (0 root, 1 tip) of segment i or -1; best_type = 0 if it is joined at its root, 1 at its tip.
+ * mh_chain_count / mh_chain_emit: connect_segments (add_mid, weight 0) for every segment: total points and points of the
+ *   root-side pieces, then (out_offsets = exclusive scan of total) the connected strands.
+ * mh_occ_check: attempt 0 of the occupancy loop (:514-544): status 1 accepted, 0 rejected (the caller draws and retries),
+ *   2 outside the reference's fixed 256x256x192 box, 3 an index the reference's torch indexing refuses.  occ [Z,H,W]
+ *   float32 with element stride occ_stride; vmin = float64 of the float32 voxel_min.
+ * mh_smooth_strands: smnooth_strand (fix_tips False), one lane per strand: pts holds b = strand * pos_constraint on entry
+ *   (formed in the strand's own dtype, as the reference's numpy does) and the solution on return; work: 3*P doubles. */
+int mh_end_knn64(mh_ctx *ctx, const double *q, const int32_t *qcell, int nq, const double *data, const int32_t *order,
+                 const int32_t *cstart, int gx, int gy, int gz, double bound, int skip_self, int32_t *out_idx,
+                 double *out_dist, int32_t *out_cnt, void *stream);
+int mh_connect_candidates(mh_ctx *ctx, const double *pts, const long long *offsets, int n, const int32_t *const *nei_idx,
+                          const double *const *nei_dist, const int32_t *const *nei_cnt, double dot_threshold,
+                          int32_t *best, int32_t *best_type, void *stream);
+int mh_chain_count(mh_ctx *ctx, const long long *offsets, int n, const int32_t *best, const int32_t *best_type,
+                   long long *total, long long *root_len, void *stream);
+int mh_chain_emit(mh_ctx *ctx, const double *pts, const long long *offsets, int n, const int32_t *best,
+                  const int32_t *best_type, const long long *root_len, const long long *out_offsets, double *out,
+                  void *stream);
+int mh_occ_check(mh_ctx *ctx, const double *pts, const long long *offsets, int n, const float *occ, long long occ_stride,
+                 int W, int H, int Z, double vmin_x, double vmin_y, double vmin_z, double voxel_size, int32_t *status,
+                 void *stream);
+int mh_smooth_strands(mh_ctx *ctx, double *pts, const long long *offsets, int n, double lap_constraint,
+                      double pos_constraint, double *work, void *stream);
 
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of

@@ -57,6 +57,13 @@ _SIGS = {
     "mh_trace_scalp": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, cf, vp, vp, vp]),
     "mh_strands_accept": (ci, [ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp]),
     "mh_strands_compact": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp]),
+    "mh_end_knn64": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ctypes.c_double, ci, vp, vp, vp, vp]),
+    "mh_connect_candidates": (ci, [vp, vp, vp, ci, vp, vp, vp, ctypes.c_double, vp, vp, vp]),
+    "mh_chain_count": (ci, [vp, vp, ci, vp, vp, vp, vp, vp]),
+    "mh_chain_emit": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "mh_occ_check": (ci, [vp, vp, vp, ci, vp, cll, ci, ci, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                          ctypes.c_double, vp, vp]),
+    "mh_smooth_strands": (ci, [vp, vp, vp, ci, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

@@ -198,6 +198,16 @@ int mh_launch_strands_compact(const float *, const int32_t *, const int32_t *, c
                               hipStream_t);
 int mh_launch_trace_scalp(const float4 *, int, int, int, const float *, const float *, int, float, float *, int32_t *,
                           hipStream_t);
+int mh_launch_end_knn64(const double *, const int32_t *, int, const double *, const int32_t *, const int32_t *, int, int,
+                        int, double, int, int32_t *, double *, int32_t *, hipStream_t);
+int mh_launch_connect_cand(const double *, const int64_t *, int, const int32_t *const *, const double *const *,
+                           const int32_t *const *, double, int32_t *, int32_t *, hipStream_t);
+int mh_launch_chain_count(const int64_t *, int, const int32_t *, const int32_t *, int64_t *, int64_t *, hipStream_t);
+int mh_launch_chain_emit(const double *, const int64_t *, int, const int32_t *, const int32_t *, const int64_t *,
+                         const int64_t *, double *, hipStream_t);
+int mh_launch_occ_check(const double *, const int64_t *, int, const float *, int64_t, int, int, int, double, double, double,
+                        double, int32_t *, hipStream_t);
+int mh_launch_smooth(double *, const int64_t *, int, double, double, double *, hipStream_t);
 }
 
 static thread_local char g_err[512] = "";
@@ -1098,6 +1108,75 @@ extern "C" int mh_strands_accept(int W, int H, int Z, float *flag, const float *
     }
     delete[] stamp;
     return MH_OK;
+}
+
+// ---- segment connection and smoothing (HairGrow.py:303-590, Utils/Utils.py:1148-1198), float64 ----------------------
+extern "C" int mh_end_knn64(mh_ctx *ctx, const double *q, const int32_t *qcell, int nq, const double *data,
+                            const int32_t *order, const int32_t *cstart, int gx, int gy, int gz, double bound,
+                            int skip_self, int32_t *out_idx, double *out_dist, int32_t *out_cnt, void *stream) {
+    if (nq == 0) return MH_OK;
+    if (!ctx || !q || !qcell || !data || !order || !cstart || !out_idx || !out_dist || !out_cnt || nq < 0 || gx < 1 ||
+        gy < 1 || gz < 1 || (long long)gx * gy * gz >= (1ll << 31) || !(bound > 0.0))
+        return fail(MH_ERR_ARG, "mh_end_knn64: bad arguments");
+    return launched(mh_launch_end_knn64(q, qcell, nq, data, order, cstart, gx, gy, gz, bound * bound, skip_self, out_idx,
+                                        out_dist, out_cnt, (hipStream_t)stream),
+                    "mh_end_knn64");
+}
+
+extern "C" int mh_connect_candidates(mh_ctx *ctx, const double *pts, const long long *offsets, int n,
+                                     const int32_t *const *nei_idx, const double *const *nei_dist,
+                                     const int32_t *const *nei_cnt, double dot_threshold, int32_t *best,
+                                     int32_t *best_type, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !nei_idx || !nei_dist || !nei_cnt || !best || !best_type || n < 0 ||
+        n > (1 << 29))
+        return fail(MH_ERR_ARG, "mh_connect_candidates: bad arguments");
+    for (int t = 0; t < 4; ++t)
+        if (!nei_idx[t] || !nei_dist[t] || !nei_cnt[t]) return fail(MH_ERR_ARG, "mh_connect_candidates: list %d is NULL", t);
+    return launched(mh_launch_connect_cand(pts, (const int64_t *)offsets, n, nei_idx, nei_dist, nei_cnt, dot_threshold,
+                                           best, best_type, (hipStream_t)stream),
+                    "mh_connect_candidates");
+}
+
+extern "C" int mh_chain_count(mh_ctx *ctx, const long long *offsets, int n, const int32_t *best, const int32_t *best_type,
+                              long long *total, long long *root_len, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !offsets || !best || !best_type || !total || !root_len || n < 0)
+        return fail(MH_ERR_ARG, "mh_chain_count: bad arguments");
+    return launched(mh_launch_chain_count((const int64_t *)offsets, n, best, best_type, (int64_t *)total,
+                                          (int64_t *)root_len, (hipStream_t)stream),
+                    "mh_chain_count");
+}
+
+extern "C" int mh_chain_emit(mh_ctx *ctx, const double *pts, const long long *offsets, int n, const int32_t *best,
+                             const int32_t *best_type, const long long *root_len, const long long *out_offsets,
+                             double *out, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !best || !best_type || !root_len || !out_offsets || !out || n < 0)
+        return fail(MH_ERR_ARG, "mh_chain_emit: bad arguments");
+    return launched(mh_launch_chain_emit(pts, (const int64_t *)offsets, n, best, best_type, (const int64_t *)root_len,
+                                         (const int64_t *)out_offsets, out, (hipStream_t)stream),
+                    "mh_chain_emit");
+}
+
+extern "C" int mh_occ_check(mh_ctx *ctx, const double *pts, const long long *offsets, int n, const float *occ,
+                            long long occ_stride, int W, int H, int Z, double vmin_x, double vmin_y, double vmin_z,
+                            double voxel_size, int32_t *status, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !occ || !status || n < 0 || occ_stride < 1 || W < 1 || H < 1 || Z < 1)
+        return fail(MH_ERR_ARG, "mh_occ_check: bad arguments");
+    return launched(mh_launch_occ_check(pts, (const int64_t *)offsets, n, occ, occ_stride, W, H, Z, vmin_x, vmin_y, vmin_z,
+                                        voxel_size, status, (hipStream_t)stream),
+                    "mh_occ_check");
+}
+
+extern "C" int mh_smooth_strands(mh_ctx *ctx, double *pts, const long long *offsets, int n, double lap_constraint,
+                                 double pos_constraint, double *work, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !work || n < 0) return fail(MH_ERR_ARG, "mh_smooth_strands: bad arguments");
+    return launched(mh_launch_smooth(pts, (const int64_t *)offsets, n, lap_constraint, pos_constraint, work,
+                                     (hipStream_t)stream),
+                    "mh_smooth_strands");
 }
 
 static int gabor_alloc(mh_ctx *ctx) {

@@ -1,8 +1,9 @@
 """Strand tracing on the fitted orientation/occupancy volume -- host-side mirror of the tracing half of the
 reference's `HairGrow.py::class HairGrowing` (__init__ :41-55, trace :59-149, traceFromScalp :154-223,
 GenerateGuideStrandFromScalp :226-265, randomlyGenerateSegments :269-299, VoxelToWorld :816-824), the immediate
-consumer of Ori3D.mat / Occ3D.mat.  Segment connection and scalp attachment
-(HairGrow.py:303-786) are not part of this package.
+consumer of Ori3D.mat / Occ3D.mat, and the segment connection that follows it
+(find_connect_info :434-590 with connect_segments :303-420, the connect_segments stage of __main__ :925-952).  Scalp
+attachment (connect_scalp, HairGrow.py:593-786) is not part of this package.
 
 All seeds are traced in parallel by the HIP kernels of csrc/hairgrow.hip; the sequential `flag` gate only decides
 which finished traces are kept and is replayed afterwards (mh_strands_accept).  The jitter of every trace() call
@@ -14,11 +15,47 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pmvo_utils import _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, save_hair_strands, voxel_to_points
+from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
+                         save_hair_strands, voxel_to_points)
+from .strand_smooth import smooth_strands
+
+_KNN_K = 50                                                      # k of the reference's end queries
+_VMIN64 = np.array([-0.32, -0.32, -0.24], np.float32).astype(np.float64)   # points_to_voxel's float32 voxel_min
+_TYPES = ("root", "tip")
 
 
 def _hp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _end_cells(ends, bound):
+    """Uniform grid over the strand ends with cells no smaller than `bound` (so every end closer than the bound lies in
+    one of the 27 cells around a query's), coarsened while it would have more than max(4n, 2^20) cells."""
+    lo = ends.min(0)
+    h = bound * 1.0001
+    cap = max(4 * ends.shape[0], 1 << 20)
+    while True:
+        cell = np.floor((ends - lo) / h).astype(np.int64)
+        dims = cell.max(0) + 1
+        if int(np.prod(dims)) <= cap:
+            return cell.astype(np.int32), [int(d) for d in dims]
+        h *= 2.0
+
+
+def _occ_eval_host(ss, occ_h):
+    """One attempt of the occupancy test (HairGrow.py:517-528) on the host: 1 accepted, 0 rejected, 2 outside the
+    reference's fixed box; raises where torch's indexing would."""
+    p = ss.copy()
+    p[:, 1:] *= -1
+    idx = np.rint((p - _VMIN64) / VOXEL_SIZE).astype(np.int64)
+    if idx[:, 2].max() >= 192 or (idx[:, 1] >= 256).any() or (idx[:, 0] >= 256).any():
+        return 2
+    Z, H, W = occ_h.shape
+    if (idx < -np.array([W, H, Z])).any() or (idx >= np.array([W, H, Z])).any():
+        raise _lib.MhError("find_connect_info: a strand indexes outside the occupancy volume (the reference's torch "
+                           "indexing raises IndexError here)")
+    v = occ_h[idx[:, 2], idx[:, 1], idx[:, 0]]
+    return 1 if np.float32(v.sum(dtype=np.float32)) / np.float32(v.shape[0]) > np.float32(0.8) else 0
 
 
 class HairGrowing:
@@ -151,6 +188,121 @@ class HairGrowing:
         self.strands = self._to_device_views(self._voxel_rounds(flag, thrDot, 3))
         return self.strands
 
+    def find_connect_info(self, strands, connect_threshold=0.005, connect_dot_threshold=0.7, occ=None):
+        """HairGrow.py:434-547: joins the segments (list of float64 [L,3] arrays in world units, L >= 2) into strands and
+        returns them.  occ: [1,Z,H,W] occupancy (0/1 values) or None for the solver's own.  The connection table is left
+        in self.connect_info (the reference's strands_connect_info: per segment {'root': [j, 'root'|'tip'] or None,
+        'tip': ...}), the failure count in self.connect_fail.  Strands that fail the first occupancy test are retried on
+        the host in segment order with np.random's global generator, exactly as the reference draws."""
+        N = len(strands)
+        self.connect_info, self.connect_fail = [], 0
+        if N == 0:
+            return []
+        arrs = [np.asarray(s, dtype=np.float64) for s in strands]
+        if any(a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 2 for a in arrs):
+            raise _lib.MhError("find_connect_info: every strand must be [L,3] with L >= 2")
+        thr = float(connect_threshold)
+        if not (thr > 0 and np.isfinite(thr)):
+            raise _lib.MhError("find_connect_info: connect_threshold must be positive and finite")
+        lens = np.array([a.shape[0] for a in arrs], np.int64)
+        offs = np.zeros(N + 1, np.int64)
+        np.cumsum(lens, out=offs[1:])
+        pts = np.ascontiguousarray(np.concatenate(arrs, 0))
+        if not np.isfinite(pts).all():
+            raise _lib.MhError("find_connect_info: non-finite strand points")
+        roots = np.ascontiguousarray(pts[offs[:-1]])
+        tips = np.ascontiguousarray(pts[offs[1:] - 1])
+        cells, dims = _end_cells(np.concatenate([roots, tips], 0), thr)
+        ncell = dims[0] * dims[1] * dims[2]
+        lin = (cells[:, 2].astype(np.int64) * dims[1] + cells[:, 1]) * dims[0] + cells[:, 0]
+        dev, L, ctx = self.device, _lib.lib(), self._ctx
+        td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)    # noqa: E731
+        pts_d, offs_d = td(pts), td(offs)
+        ends_d = [td(roots), td(tips)]
+        qcell_d = [td(cells[:N]), td(cells[N:])]
+        grids = []
+        for t in range(2):          # 0: the roots' tree, 1: the tips'
+            l = lin[t * N:(t + 1) * N]
+            order = np.argsort(l, kind="stable").astype(np.int32)
+            cstart = np.zeros(ncell + 1, np.int32)
+            np.cumsum(np.bincount(l, minlength=ncell), out=cstart[1:])
+            grids.append((td(order), td(cstart)))
+        lists = []
+        with torch.cuda.device(dev):
+            for qe, te in ((0, 0), (0, 1), (1, 0), (1, 1)):   # root->roots, root->tips, tip->roots, tip->tips
+                idx = torch.empty((N, _KNN_K), dtype=torch.int32, device=dev)
+                dist = torch.empty((N, _KNN_K), dtype=torch.float64, device=dev)
+                cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+                _lib.check(L.mh_end_knn64(ctx, _lib.ptr(ends_d[qe]), _lib.ptr(qcell_d[qe]), N, _lib.ptr(ends_d[te]),
+                                          _lib.ptr(grids[te][0]), _lib.ptr(grids[te][1]), dims[0], dims[1], dims[2],
+                                          thr, 1, _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(cnt), _lib.stream_ptr()),
+                           "mh_end_knn64")
+                lists.append((idx, dist, cnt))
+            self._end_lists = lists
+            arr = lambda k: (ctypes.c_void_p * 4)(*[l[k].data_ptr() for l in lists])   # noqa: E731
+            best = torch.empty((2 * N,), dtype=torch.int32, device=dev)
+            btype = torch.empty((2 * N,), dtype=torch.int32, device=dev)
+            _lib.check(L.mh_connect_candidates(ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, arr(0), arr(1), arr(2),
+                                               float(connect_dot_threshold), _lib.ptr(best), _lib.ptr(btype),
+                                               _lib.stream_ptr()), "mh_connect_candidates")
+            total = torch.empty((N,), dtype=torch.int64, device=dev)
+            rootlen = torch.empty((N,), dtype=torch.int64, device=dev)
+            _lib.check(L.mh_chain_count(ctx, _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype), _lib.ptr(total),
+                                        _lib.ptr(rootlen), _lib.stream_ptr()), "mh_chain_count")
+            ooffs = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+            torch.cumsum(total, 0, out=ooffs[1:])
+            T = int(ooffs[-1])
+            out = torch.empty((T, 3), dtype=torch.float64, device=dev)
+            _lib.check(L.mh_chain_emit(ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype),
+                                       _lib.ptr(rootlen), _lib.ptr(ooffs), _lib.ptr(out), _lib.stream_ptr()),
+                       "mh_chain_emit")
+            if occ is None:
+                occ_t, ostride = self._vox, 4          # channel 3 of the packed voxels = self.occ
+                Z, H, W = self.Z, self.H, self.W
+                occ_base = occ_t.data_ptr() + 3 * 4
+            else:
+                occ_t = torch.as_tensor(occ).to(dev).float().contiguous()
+                Z, H, W = occ_t.shape[-3:]
+                ostride, occ_base = 1, occ_t[0].data_ptr() if occ_t.dim() == 4 else occ_t.data_ptr()
+            status = torch.empty((N,), dtype=torch.int32, device=dev)
+            _lib.check(L.mh_occ_check(ctx, _lib.ptr(out), _lib.ptr(ooffs), N, ctypes.c_void_p(occ_base), ostride, W, H,
+                                      Z, float(_VMIN64[0]), float(_VMIN64[1]), float(_VMIN64[2]), VOXEL_SIZE,
+                                      _lib.ptr(status), _lib.stream_ptr()), "mh_occ_check")
+            out_h, oo_h, st_h = out.cpu().numpy(), ooffs.cpu().numpy(), status.cpu().numpy()
+            best_h, btype_h = best.cpu().numpy().reshape(N, 2), btype.cpu().numpy().reshape(N, 2)
+        self.connect_best, self.connect_best_type = best_h, btype_h
+        self.connect_info = [{e: (None if best_h[i, k] < 0 else [int(best_h[i, k]), _TYPES[btype_h[i, k]]])
+                              for k, e in enumerate(_TYPES)} for i in range(N)]
+        occ_h = None
+        fail = 0
+        new_strands = []
+        for i in range(N):
+            strand = out_h[oo_h[i]:oo_h[i + 1]]
+            st = int(st_h[i])
+            if st == 3:
+                raise _lib.MhError("find_connect_info: a strand indexes outside the occupancy volume (the reference's "
+                                   "torch indexing raises IndexError here)")
+            if st == 0:           # the retry loop of HairGrow.py:514-544, replayed in segment order
+                if occ_h is None:
+                    occ_h = (self.occ[0] if occ is None else occ_t.reshape(Z, H, W)).cpu().numpy()
+                st = 0
+                for count in range(1, 51):
+                    ss = strand.copy()
+                    ss += np.random.random((3)) * 0.005
+                    if count >= 50:
+                        break
+                    st = _occ_eval_host(ss, occ_h)
+                    if st == 1:
+                        strand = ss
+                        break
+                    if st == 2:
+                        break
+            if st != 1:
+                fail += 1
+            new_strands.append(strand)
+        self.connect_fail = fail
+        return new_strands
+
     def VoxelToWorld(self, strands, bust_to_origin=None):
         """HairGrow.py:816-824."""
         out = []
@@ -163,15 +315,46 @@ class HairGrowing:
 
 
 def generate_segments(occ_path, ori_path, scalp_points_voxel, scalp_normals_voxel, save_path, bust_to_origin,
-                      grow_threshold=0.8, device="cuda:0"):
-    """The `generate_segments` stage of HairGrow.py's __main__ (:897-907, without the Laplacian smoothing pass):
-    scalp_segment.hair + num_root.npy."""
+                      grow_threshold=0.8, device="cuda:0", write_smooth=False, occ=None, ori=None):
+    """The `generate_segments` stage of HairGrow.py's __main__ (:897-920): scalp_segment.hair + num_root.npy, and with
+    write_smooth also the Laplacian-smoothed copy scalp_segment_smooth.hair (:914-917).  occ / ori: the readers' arrays
+    in place of the two files.  Returns the unsmoothed segments."""
     import os
 
-    solver = HairGrowing(occ_path, ori_path, device=device)
+    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
     strands, num_root = solver.GenerateGuideStrandFromScalp(scalp_points_voxel, scalp_normals_voxel, None,
                                                             grow_threshold)
     world = solver.VoxelToWorld(strands, bust_to_origin)
     save_hair_strands(os.path.join(save_path, "scalp_segment.hair"), world, bust_to_origin, translate=False)
+    if write_smooth:
+        smooth = smooth_strands(list(world), 4.0, 2.0, device=device)
+        save_hair_strands(os.path.join(save_path, "scalp_segment_smooth.hair"), smooth, bust_to_origin, translate=False)
     np.save(os.path.join(save_path, "num_root.npy"), np.array(num_root))
     return world, num_root
+
+
+def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect_dot_threshold=0.7, occ_path=None,
+                     ori_path=None, device="cuda:0", occ=None, ori=None):
+    """The `connect_segments` stage of HairGrow.py's __main__ (:925-952): reads scalp_segment.hair and num_root.npy
+    from save_path, joins the non-root segments (shifted by bust_to_origin) with find_connect_info on the volume of
+    occ_path / ori_path (or the arrays occ / ori), smooths every strand (4.0, 2.0) and writes strands.hair.  Returns
+    (strands, solver)."""
+    import os
+
+    segment, points = load_strand(os.path.join(save_path, "scalp_segment.hair"))
+    num_root = int(np.load(os.path.join(save_path, "num_root.npy")))
+    bust = np.asarray(bust_to_origin, dtype=np.float64)
+    strands = []
+    beg = 0
+    for i, seg in enumerate(segment):
+        strand = points[beg:beg + seg]
+        if i >= num_root:
+            strand += bust
+        strands.append(strand)
+        beg += seg
+    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
+    connected = solver.find_connect_info(strands[num_root:], connect_threshold, connect_dot_threshold)
+    new_strands = strands[:num_root] + [c - bust for c in connected]
+    new_strands = smooth_strands(new_strands, 4.0, 2.0, device=device)
+    save_hair_strands(os.path.join(save_path, "strands.hair"), new_strands, bust, translate=False)
+    return new_strands, solver

@@ -1,0 +1,47 @@
+"""Laplacian smoothing of strands -- Utils/Utils.py:1148-1198 (smnooth_strand / smooth_strands) on the GPU.
+
+The reference solves (A^T A) x = A^T b with scipy's spsolve (SuperLU) once per strand and axis; A^T A is pentadiagonal
+plus pos^2 I, and csrc/hairconnect.hip solves it with a float64 banded Cholesky in LAPACK's order (scipy's
+solveh_banded), one lane per strand.  The two solvers round differently in float64; what is pinned is the float32 `.hair`
+file written from the result."""
+import numpy as np
+import torch
+
+from . import _lib
+from .pmvo_utils import _ctx_for
+
+
+def smooth_strands(strands, lap_constraint=2.0, pos_constraint=1.0, fix_tips=False, device="cuda:0"):
+    """Utils.py:1191-1198: replaces every strands[i] ([L,3], L >= 2) by its smoothed copy, in place on the list (with
+    fix_tips, strands[i][1:-1] is overwritten instead), and returns the list."""
+    if not strands:
+        return strands
+    if not torch.cuda.is_available():
+        raise _lib.MhError("smooth_strands needs a ROCm GPU (no CPU fallback)")
+    arrs = [np.asarray(s) for s in strands]
+    lens = np.array([a.shape[0] for a in arrs], np.int64)
+    if lens.min() < 2 or any(a.ndim != 2 or a.shape[1] != 3 for a in arrs):
+        raise _lib.MhError("smooth_strands: every strand must be [L,3] with L >= 2")
+    offs = np.zeros(len(arrs) + 1, np.int64)
+    np.cumsum(lens, out=offs[1:])
+    # b[num_pts:] = smoothed_strand[:, axis] * pos_constraint, evaluated in the strand's dtype like the reference
+    rhs = np.concatenate([(a * pos_constraint).astype(np.float64) for a in arrs], 0)
+    dev = torch.device(device)
+    pts = torch.from_numpy(np.ascontiguousarray(rhs)).to(dev)
+    offs_d = torch.from_numpy(offs).to(dev)
+    work = torch.empty((3 * int(offs[-1]),), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mh_smooth_strands(_ctx_for(dev), _lib.ptr(pts), _lib.ptr(offs_d), len(arrs),
+                                                float(lap_constraint), float(pos_constraint), _lib.ptr(work),
+                                                _lib.stream_ptr()), "mh_smooth_strands")
+    sol = pts.cpu().numpy()
+    for i, a in enumerate(arrs):
+        x = sol[offs[i]:offs[i + 1]]
+        if fix_tips:
+            a[1:-1] = x[1:-1]
+            strands[i] = a
+        else:
+            sm = np.copy(a)
+            sm[:] = x
+            strands[i] = sm
+    return strands

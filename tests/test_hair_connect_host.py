@@ -1,0 +1,62 @@
+"""CPU-only: the segment-connection fixture (tests/golden/hair_connect.npz) is consistent with the stage it records --
+strands.hair is write_strand of the recorded connected strands after the float64 subtraction of bust_to_origin and the
+Laplacian smoothing (restated with scipy's banded solver, whose float32 rounding is what the file pins)."""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN
+
+
+def _smooth(s, lap, pos):
+    from scipy.linalg import solveh_banded
+
+    n = s.shape[0]
+    A = np.zeros((2 * n, n))
+    A[0, :2] = [lap, -lap]
+    for k in range(1, n - 1):
+        A[k, k - 1:k + 2] = [-lap, 2 * lap, -lap]
+    A[n - 1, n - 2:] = [-lap, lap]
+    A[n:] = np.eye(n) * pos
+    M = A.T @ A
+    ab = np.zeros((3, n))
+    for u in range(3):
+        ab[2 - u, u:] = np.diagonal(M, u)
+    return solveh_banded(ab, (s * pos) * pos)
+
+
+def _hair(b):
+    n = int(np.frombuffer(b[:4], "<u4")[0])
+    lens = np.frombuffer(b[8:8 + 2 * n], "<u2").astype(int)
+    pts = np.frombuffer(b[8 + 2 * n:], "<f4").reshape(-1, 3)
+    assert int(np.frombuffer(b[4:8], "<u4")[0]) == lens.sum() == pts.shape[0]
+    return lens, pts
+
+
+def test_fixture_strands_hair_is_smoothed_recorded_strands(tmp_path):
+    pytest.importorskip("scipy")
+    from monohair_amd.pmvo_utils import write_strand
+
+    z = np.load(os.path.join(GOLDEN, "hair_connect.npz"))
+    lens, pts = _hair(z["seg_hair"].tobytes())
+    segs = np.split(pts.astype(np.float64), np.cumsum(lens)[:-1])
+    nr = int(z["num_root"])
+    out = np.split(z["shell_out_pts"], np.cumsum(z["shell_out_len"])[:-1])
+    assert len(out) == len(segs) - nr
+    strands = segs[:nr] + [c - z["bust"] for c in out]
+    sm = [_smooth(s, 4.0, 2.0) for s in strands]
+    write_strand(np.concatenate(sm, 0), str(tmp_path / "strands.hair"), [s.shape[0] for s in sm])
+    assert (tmp_path / "strands.hair").read_bytes() == z["strands_hair"].tobytes()
+
+
+def test_fixture_covers_the_edge_cases():
+    z = np.load(os.path.join(GOLDEN, "hair_connect.npz"))
+    assert (z["edge_rr_idx"] >= 0).sum(1).max() >= 49                      # a full k = 50 row (self dropped)
+    assert ((z["edge_rr_idx"] < 0).all(1) & (z["edge_rt_idx"] < 0).all(1)).any()   # empty lists
+    d = z["edge_draws"]
+    assert (d == 50).any() and ((d > 0) & (d < 50)).any()                # exhausted and successful retries
+    assert int(z["edge_fail"]) > int((d == 50).sum())                     # failures without retries: outside the box
+    table = z["edge_table"]
+    ring = range(60, 68)
+    assert all(table[i, 1, 0] >= 0 for i in ring)                         # the ring joins into a cycle
