@@ -60,3 +60,55 @@ def test_fixture_covers_the_edge_cases():
     table = z["edge_table"]
     ring = range(60, 68)
     assert all(table[i, 1, 0] >= 0 for i in ring)                         # the ring joins into a cycle
+
+
+# ------------------------------------------------------------------ the restatement the GPU sweep compares against
+def _occ_zyx(z):
+    G = tuple(int(g) for g in z["vol_shape"])
+    occ = np.zeros(G, np.float32)
+    occ[tuple(z["occ_nz"].T.astype(np.int64))] = 1
+    return np.ascontiguousarray(occ.transpose(2, 1, 0))
+
+
+@pytest.mark.parametrize("tag,seed", [("shell", 1234), ("edge", 99), ("long", 4321)])
+def test_numpy_restatement_reproduces_the_reference(tag, seed):
+    """The float64 numpy restatement of find_best_connect_strands / connect_segments / the occupancy loop kept in
+    test_hair_connect_gpu.py gives the reference's recorded table, connected strands, fail count and next np.random
+    value exactly, on the two cases of hair_connect.npz and on the "long" case of strands_long.npz (segments of up to
+    513 points, strands of more than 1000); that licenses it as the comparator of the GPU sweep."""
+    import test_hair_connect_gpu as T
+
+    if tag == "long":
+        z = np.load(os.path.join(GOLDEN, "strands_long.npz"))
+        segs, occ, thr, dot = T._long_case(z)
+    else:
+        z = np.load(os.path.join(GOLDEN, "hair_connect.npz"))
+        segs = T._shell_segments(z)[0] if tag == "shell" else T._split(z["edge_in_pts"], z["edge_in_len"])
+        occ, thr, dot = _occ_zyx(z), float(z["thr"]), float(z["dot"])
+    np.random.seed(seed)
+    table, _, out, fail = T._rs_connect(segs, thr, dot, occ, T._stats())
+    assert np.random.random() == float(z[tag + "_next_random"])
+    assert np.array_equal(table, z[tag + "_table"])
+    ref = T._split(z[tag + "_out_pts"], z[tag + "_out_len"])
+    assert len(out) == len(ref) and all(np.array_equal(a, b) for a, b in zip(out, ref))
+    assert fail == int(z[tag + "_fail"])
+
+
+def test_sweep_inputs_reach_every_situation():
+    """the inputs of the GPU sweep, judged by the restatement alone: every situation the sweep exists for occurs"""
+    import test_hair_connect_gpu as T
+
+    z = np.load(os.path.join(GOLDEN, "hair_connect.npz"))
+    occ = _occ_zyx(z)
+    rng = np.random.default_rng(2024)
+    stats = T._stats()
+    for trial in range(3):
+        segs = T._sweep_segments(rng, trial)
+        assert {len(s) for s in segs} >= set(T._SWEEP_LENS)
+        np.random.seed(500 + trial)
+        _, _, out, _ = T._rs_connect(segs, 0.005, 0.7, occ, stats)
+        lists = T._np_lists(segs, 0.005)
+        stats["end_ties"] += sum(len(np.unique(r[1])) < len(r[1]) for k in range(4) for r in lists[k])
+        stats["strand_gt513"] += sum(o.shape[0] > 513 for o in out)
+        stats["strand_gt1000"] += sum(o.shape[0] > 1000 for o in out)
+    T._assert_sweep_reaches(stats)
