@@ -11,21 +11,8 @@
 #include <vector>
 
 #include "../../include/mh_pmvo.h"
-
-struct MhViews {   // = MhViews of csrc/mh_device.h
-    int V, H, W;
-    const float4 *rec;
-    const float *mask;
-    const float *cams;
-    const float4 *tap;
-    int batch_rule;
-};
-
-#define MH_DG_MAXR 48
-struct MhDogWeightsHost {          // = MhDogWeights of csrc/dog.hip
-    double w[2][MH_DG_MAXR + 1];
-    int r[2];
-};
+#include "../../include/mh_pmvo_lab.h"
+#include "mh_launch.h"
 
 struct mh_ctx {
     int device = 0;
@@ -55,7 +42,7 @@ struct mh_ctx {
     float *gabor_q = nullptr; // the same coefficients in the operand order of mh_gabor_mfma2_kernel [145][64][8]
     unsigned int *gabor_max = nullptr;
     void *dog_w = nullptr;    // device MhDogWeights of the difference-of-Gaussians prefilter (csrc/dog.hip)
-    MhDogWeightsHost *dog_w_host = nullptr;   // what dog_w holds
+    MhDogWeights *dog_w_host = nullptr;   // what dog_w holds
     float4 *lut = nullptr;    // [256] pixel-code table of the 8-bit map files
     // views uploaded as 8-bit file codes keep the codes resident as well (2 B per pixel: orientation | confidence << 8) for
     // the per-iteration tap gathers of mh_forward_prepare; used when EVERY view was uploaded that way with one table
@@ -81,14 +68,24 @@ struct mh_ctx {
     int S = 0;
     int search_variant = 0;
     int search_body = 0;      // tap body of mh_search3_kernel: 0 = by the maps (see mh_ctx_set_option), 1 = keys, 2 = select
-    // The shipped search has two tap bodies with the same results (csrc/pmvo_search.hip): the key body (5.5 instructions per
-    // evaluation, a fixed cost per view) and the compare-and-select body (7, none).  Lists of continuous maps hold ~45 taps,
-    // lists of 8-bit maps ~2 after the exact duplicate removal: the kernel that carries both bodies runs short lists 5 %
-    // slower than the select-only kernel (register allocation), so contexts whose views are all 8-bit codes get that one.
-    int search_launch_variant(int v) const {
-        if (v != 0 && v != 6 && v != 7 && v != 8 && v != 9 && v != 10) return v;   // (100.. = select body asked for; 1256 = portable kernel)
-        const bool select = search_body == 2 || (search_body == 0 && views_8bit());
-        return select ? (v == 0 ? 100 : v + 100) : v;
+    // The lab option "search_variant" (include/mh_pmvo_lab.h) in words; false: not a value of that option.
+    bool search_plan(MhSearchPlan *plan) const {
+        *plan = MhSearchPlan{false, false, MhSearchPlan::ORDER_BY_WORK, MhSearchPlan::PART_ALL};
+        switch (search_variant) {
+            case 0: case 100: break;
+            case 7: case 107: plan->order = MhSearchPlan::ORDER_NATURAL; break;
+            case 9: case 109: plan->part = MhSearchPlan::PART_PRE_ONLY; break;
+            case 10: case 110: plan->part = MhSearchPlan::PART_KERNEL_ONLY; break;
+            case 1256: plan->portable = true; break;
+            default: return false;
+        }
+        const bool select_asked = search_variant == 100 || search_variant == 107 || search_variant == 109 || search_variant == 110;
+        // The shipped search has two tap bodies with the same results (csrc/pmvo_search.hip): the key body (5.5 instructions per
+        // evaluation, a fixed cost per view) and the compare-and-select body (7, none).  Lists of continuous maps hold ~45 taps,
+        // lists of 8-bit maps ~2 after the exact duplicate removal: the kernel that carries both bodies runs short lists 5 %
+        // slower than the select-only kernel (register allocation), so contexts whose views are all 8-bit codes get that one.
+        plan->select_body = select_asked || search_body == 2 || (search_body == 0 && views_8bit());
+        return true;
     }
     // The reference's batch composition in the arithmetic (csrc/mh_device.h: MhRule, MhBatch; oracle/pmvo_oracle.c):
     int reproject_rule = 0;   // 0: sample_next_3d_pos's sgemms round by the size of the (rank, base view) group as MKL does in
@@ -104,111 +101,6 @@ struct mh_ctx {
                               // (1 and 2 named two forms removed in round 4.)
     MhViews views() const { return MhViews{V, H, W, rec, mask, cams, tap_ready(), reproject_rule == 0 ? 1 : 0}; }
 };
-
-// launchers implemented in the .hip files
-extern "C" {
-int mh_launch_pack_view(float4 *, float *, const float *, int, const float *, const float *, const float *, int,
-                        size_t, float4 *, hipStream_t);
-int mh_launch_pack_view_u8(float4 *, float *, const float *, int, const uint8_t *, const uint8_t *, const uint8_t *,
-                           const float4 *, size_t, uint16_t *, float4 *, hipStream_t);
-size_t mh_code_tabs_bytes();
-int mh_preload_pmvo_project();
-int mh_preload_pmvo_search();
-int mh_preload_pmvo_filter();
-int mh_preload_consensus();
-int mh_preload_gabor();
-int mh_preload_hairgrow();
-int mh_preload_knn();
-int mh_preload_raster();
-int mh_preload_sortgroup();
-int mh_preload_pmvo_pieces();
-int mh_preload_dog();
-
-int mh_launch_code_tabs(const float4 *, void *, hipStream_t);
-int mh_launch_render_depth(const float *, const float *, int, const int32_t *, int, int, int, int, int, void *,
-                           unsigned long long *, int32_t *, unsigned int *, float *, int, hipStream_t);
-size_t mh_grid_scratch_bytes_impl(int);
-size_t mh_sort_scratch_bytes_impl(int);
-int mh_launch_grid_build(const float *, int, float, float, float, float, int, int, int, void *, size_t, float *,
-                         int32_t *, int32_t *, int32_t *, hipStream_t);
-int mh_launch_sort_keys(const unsigned long long *, int, int, void *, size_t, unsigned long long *, int32_t *,
-                        hipStream_t);
-size_t mh_voxel_group_scratch_bytes_impl(int);
-size_t mh_select_scratch_bytes_impl(int);
-int mh_launch_select_rows(const uint8_t *, const uint8_t *, int, int, const float *, const float *, float *, float *,
-                          int32_t *, const int32_t *, int32_t *, void *, hipStream_t);
-int mh_launch_segment_heads(const unsigned long long *, int, int32_t *, unsigned long long *, int32_t *, void *,
-                            hipStream_t);
-int mh_launch_flag_less(const float *, float, int, uint8_t *, hipStream_t);
-int mh_launch_words_differ(const void *, const void *, size_t, int32_t *, hipStream_t);
-int mh_launch_copy_words(const void *, void *, size_t, hipStream_t);
-int mh_launch_points_bbox(const float *, int, float *, hipStream_t);
-int mh_launch_voxel_group(const void *, int, const float *, int, const double *, double, const int32_t *, void *, size_t,
-                          unsigned long long *, int32_t *, float *, hipStream_t);
-int mh_launch_render_strands(const float *, const float *, int, const int32_t *, int, const float *, const float *, int,
-                             int, int, int, int, int, int, int, int, float, void *, void *, unsigned long long *, int32_t *,
-                             unsigned int *, float *, hipStream_t);
-int mh_launch_project_points(const float *, const float *, int, int, int, int32_t *, float *, uint8_t *, float *, int,
-                             hipStream_t);
-int mh_launch_gather(MhViews, int, const long long *, int, int, float4 *, float *, hipStream_t);
-int mh_launch_compute_visible(const float *, const float *, size_t, float *, hipStream_t);
-int mh_launch_sample_next(MhViews, const float *, const int32_t *, const float *, const float *, int, int, float *, int, int,
-                          int32_t *,
-                          hipStream_t);
-int mh_launch_reproject(MhViews, const float *, const float *, int, int, float *, hipStream_t);
-int mh_launch_prj_loss(const float *, const float *, const float *, const float *, int, int, int, int, float, float *,
-                       long long *, uint8_t *, float *, int, hipStream_t);
-int mh_launch_project_gather(MhViews, const float *, int, int, float *, float *, float *, float *, float *, float *,
-                             float *, hipStream_t);
-int mh_launch_topk(const float *, const float *, int, int, int32_t *, float *, int, hipStream_t);
-int mh_launch_topk_work(const float *, const float *, int, int, int32_t *, float *, int, const uint8_t *, int32_t *, int, int,
-                        int, int, int32_t *, int, hipStream_t);
-int mh_launch_prep_taps(const float *, const float *, const float *, const float *, int, int, float, float4 *,
-                        uint8_t *, hipStream_t);
-int mh_launch_project_taps(MhViews, const float *, int, int, float, float *, float *, float *, float *, float4 *,
-                           uint8_t *, int, const uint16_t *, const void *, int32_t *, int, hipStream_t);
-int mh_launch_search(MhViews, const float *, int, int, int, const float *, int, int, float, const float *,
-                     const int32_t *, const float *, const float4 *, int32_t *, const uint8_t *, float *, float *,
-                     uint8_t *, float *, int32_t *, int32_t *, int, int, int, int, int32_t *, int, hipStream_t);
-int mh_launch_refine_loss(MhViews, const float *, const float *, float, float, int, int, float, const float *,
-                          const float *, const float *, float *, uint8_t *, int, hipStream_t);
-int mh_launch_filter_points(MhViews, const float *, int, int, float, float, uint8_t *, uint8_t *, uint8_t *,
-                            uint8_t *, int, long long, long long, int, int, const int32_t *, hipStream_t);
-int mh_launch_medoid_dense(const float *, const int32_t *, int, int, float *, int32_t *, hipStream_t);
-int mh_launch_refine_loss_maps(MhViews, const float *, const float *, float, float, int, int, float, float *, uint8_t *,
-                               int, long long, long long, int, hipStream_t);
-int mh_launch_refine_combine(const float *, const float *, const uint8_t *, const uint8_t *, float, float *, float *,
-                             int, hipStream_t);
-int mh_launch_medoid_segmented(const float *, const int32_t *, int, int, float *, int32_t *, hipStream_t);
-int mh_launch_gabor_bank(const float *, const float *, const float *, int, int, int32_t *, float *, float *, unsigned int *,
-                         int, uint8_t *, uint8_t *, hipStream_t);
-size_t mh_gabor_state_bytes();
-size_t mh_gabor_bankq_bytes();
-int mh_launch_gabor_relayout(const float *, float *, hipStream_t);
-int mh_launch_dog(const void *, int, int, int, const void *, double *, double *, float *, hipStream_t);
-int mh_launch_gabor_build(float *, hipStream_t);
-int mh_launch_replace_dissimilar(const float *, float *, float, int, hipStream_t);
-int mh_launch_knn(float, float, float, float, int, int, int, const float *, const int32_t *, const int32_t *,
-                  const void *, int, int, int, int, const int32_t *, const uint8_t *, int32_t *, int32_t *, hipStream_t);
-int mh_launch_nearest_dist(const float *, int, const double *, int, double *, double, double, uint8_t *, hipStream_t);
-int mh_launch_pack_volume(const float *, const float *, size_t, float4 *, hipStream_t);
-int mh_launch_trace_seeds(const float4 *, int, int, int, const float *, int, float, float *, int32_t *, int32_t *,
-                          hipStream_t);
-int mh_launch_strands_compact(const float *, const int32_t *, const int32_t *, const int64_t *, int, int, float *,
-                              hipStream_t);
-int mh_launch_trace_scalp(const float4 *, int, int, int, const float *, const float *, int, float, float *, int32_t *,
-                          hipStream_t);
-int mh_launch_end_knn64(const double *, const int32_t *, int, const double *, const int32_t *, const int32_t *, int, int,
-                        int, double, int, int32_t *, double *, int32_t *, hipStream_t);
-int mh_launch_connect_cand(const double *, const int64_t *, int, const int32_t *const *, const double *const *,
-                           const int32_t *const *, double, int32_t *, int32_t *, hipStream_t);
-int mh_launch_chain_count(const int64_t *, int, const int32_t *, const int32_t *, int64_t *, int64_t *, hipStream_t);
-int mh_launch_chain_emit(const double *, const int64_t *, int, const int32_t *, const int32_t *, const int64_t *,
-                         const int64_t *, double *, hipStream_t);
-int mh_launch_occ_check(const double *, const int64_t *, int, const float *, int64_t, int, int, int, double, double, double,
-                        double, int32_t *, hipStream_t);
-int mh_launch_smooth(double *, const int64_t *, int, double, double, double *, hipStream_t);
-}
 
 static thread_local char g_err[512] = "";
 
@@ -412,7 +304,7 @@ extern "C" int mh_render_depth(mh_ctx *ctx, const float *cam_host, const float *
     float *cam = (float *)base;
     MH_HIP(hipMemcpyAsync(cam, cam_host, MH_CAM_STRIDE * sizeof(float), hipMemcpyHostToDevice, st));
     unsigned int *qcount = (unsigned int *)(base + 256);
-    void *vt = base + 512;
+    MhRVert *vt = (MhRVert *)(base + 512);
     unsigned long long *zbuf = (unsigned long long *)(base + 512 + render_vt_bytes(Nv));
     int32_t *queue = (int32_t *)((char *)zbuf + (size_t)H * W * sizeof(unsigned long long));
     const int off = (int)(pixel_center * 256.0f + 0.5f);
@@ -445,10 +337,10 @@ extern "C" int mh_render_strands(mh_ctx *ctx, const float *cam_host, const float
     float *cam = (float *)base;
     MH_HIP(hipMemcpyAsync(cam, cam_host, MH_CAM_STRIDE * sizeof(float), hipMemcpyHostToDevice, st));
     unsigned int *qcount = (unsigned int *)(base + 256);
-    void *vt = base + 512;
+    MhRVert *vt = (MhRVert *)(base + 512);
     unsigned long long *zbuf = (unsigned long long *)(base + 512 + render_vt_bytes(Nv));
     int32_t *queue = (int32_t *)((char *)zbuf + (size_t)H * W * sizeof(unsigned long long));
-    char *lv = base + ((mh_render_scratch_bytes(Nv, Nf, H, W) + 63) / 64) * 64;
+    MhRLVert *lv = (MhRLVert *)(base + ((mh_render_scratch_bytes(Nv, Nf, H, W) + 63) / 64) * 64);
     const int off = (int)(pixel_center * 256.0f + 0.5f);
     return launched(mh_launch_render_strands(cam, verts, Nv, faces, Nf, line_pts, line_tan, Nseg, H, W, off,
                                              1 << ctx->raster_subpixel_bits, line_width, ctx->line_rule, color_option, depth_option, clear, vt, lv, zbuf, queue, qcount,
@@ -599,8 +491,8 @@ static size_t search_count_offset(const mh_ctx *ctx, int N, int patch) {
     return search_order_offset(ctx, N, patch) + 2 * (size_t)N * sizeof(int32_t);
 }
 
-// behind the list lengths: the points per (rank, base view) of the batch (16 partial copies x 16 ranks x V ints) --
-// csrc/mh_device.h: MhRule
+// behind the list lengths: the points per (rank, base view) of the batch (MH_GROUP_COPIES partial copies x MH_GROUP_RANKS
+// ranks x V ints) -- csrc/mh_device.h: MhRule
 static size_t search_groups_offset(const mh_ctx *ctx, int N, int patch) {
     return (search_count_offset(ctx, N, patch) + (size_t)ctx->V * (size_t)N + 255) & ~(size_t)255;
 }
@@ -616,7 +508,7 @@ extern "C" size_t mh_search_scratch_bytes(mh_ctx *ctx, int N, int patch) {
     // + 2N ints behind them: the launch order of the search (mh_search_order_kernel) and its staging area
     // + V*N bytes: the list lengths once more, compact, for the work estimate
     // + the group sizes of the batch (search_groups_offset)
-    return search_groups_offset(ctx, N, patch) + (size_t)16 * 16 * ctx->V * sizeof(int32_t);
+    return search_groups_offset(ctx, N, patch) + (size_t)MH_GROUP_COPIES * MH_GROUP_RANKS * ctx->V * sizeof(int32_t);
 }
 
 extern "C" int mh_search_forward(mh_ctx *ctx, const float *points, int N, int patch, float conf_threshold, int nrank,
@@ -644,13 +536,14 @@ extern "C" int mh_search_forward(mh_ctx *ctx, const float *points, int N, int pa
                                           (uint8_t *)scratch + search_count_offset(ctx, N, patch), st),
                       "mh_search_forward(prep)");
     if (rc) return rc;
+    MhSearchPlan plan;
+    if (!ctx->search_plan(&plan)) return fail(MH_ERR_ARG, "mh_search_forward: unknown search_variant %d", ctx->search_variant);
     return launched(mh_launch_search(ctx->views(), ctx->offs, ctx->S, nrank, rank_step, points, N, P + 1,
                                      conf_threshold, ori, base_idx, base_val, (const float4 *)scratch,
                                      (int32_t *)((char *)scratch + search_order_offset(ctx, N, patch)),
                                      (const uint8_t *)scratch + search_count_offset(ctx, N, patch), line_ori,
                                      min_loss, high_conf, best_sample, best_rank, best_s,
-                                     ctx->search_launch_variant(ctx->search_variant), ctx->reproject_rule,
-                                     ctx->reproject_fma_min_cols, ctx->sum_block,
+                                     plan, ctx->reproject_rule, ctx->reproject_fma_min_cols, ctx->sum_block,
                                      (int32_t *)((char *)scratch + search_groups_offset(ctx, N, patch)), 0, st),
                     "mh_search_forward");
 }
@@ -668,7 +561,7 @@ static int forward_prepare(mh_ctx *ctx, const float *points, int N, int patch, f
                                            (uint8_t *)scratch + search_count_offset(ctx, N, patch), ctx->taps_tile,
                                            ctx->codes_ready() ? ctx->oc : nullptr, ctx->code_tabs,
                                            (int32_t *)((char *)scratch + search_groups_offset(ctx, N, patch)),
-                                           zero_groups ? 16 * 16 * ctx->V : 0, (hipStream_t)stream),
+                                           zero_groups ? MH_GROUP_COPIES * MH_GROUP_RANKS * ctx->V : 0, (hipStream_t)stream),
                     "mh_forward_prepare");
 }
 
@@ -681,7 +574,7 @@ extern "C" int mh_forward_prepare(mh_ctx *ctx, const float *points, int N, int p
 static int search_prepared(mh_ctx *ctx, const float *points, int N, int patch, float conf_threshold, int nrank,
                            int rank_step, const float *ori, const int32_t *base_idx, const float *base_val,
                            void *scratch, float *line_ori, float *min_loss, uint8_t *high_conf,
-                           float *best_sample, int32_t *best_rank, int32_t *best_s, int variant, int groups_ready,
+                           float *best_sample, int32_t *best_rank, int32_t *best_s, bool classes_ready, int groups_ready,
                            void *stream) {
     if (!ctx || !ctx->rec) return fail(MH_ERR_STATE, "mh_search_prepared: views not set");
     if (!ctx->offs) return fail(MH_ERR_STATE, "mh_search_prepared: depth offsets not set");
@@ -690,14 +583,17 @@ static int search_prepared(mh_ctx *ctx, const float *points, int N, int patch, f
         nrank < 1 || rank_step < 1 || (nrank - 1) * rank_step >= MH_TOPK)
         return fail(MH_ERR_ARG, "mh_search_prepared: bad arguments");
     if (ctx->V >= 4096) return fail(MH_ERR_ARG, "mh_search_prepared: V >= 4096 needs a fourth cascade level");
+    MhSearchPlan plan;
+    if (!ctx->search_plan(&plan)) return fail(MH_ERR_ARG, "mh_search_prepared: unknown search_variant %d", ctx->search_variant);
+    if (classes_ready) plan.order = MhSearchPlan::ORDER_CLASSES_READY;   // (the fused forward, which runs the default plan only)
     return launched(mh_launch_search(ctx->views(), ctx->offs, ctx->S, nrank, rank_step, points, N,
                                      patch * patch + 1, conf_threshold, ori, base_idx, base_val,
                                      (const float4 *)scratch,
                                      (int32_t *)((char *)scratch + search_order_offset(ctx, N, patch)),
                                      (const uint8_t *)scratch + search_count_offset(ctx, N, patch), line_ori,
                                      min_loss, high_conf, best_sample, best_rank, best_s,
-                                     ctx->search_launch_variant(variant), ctx->reproject_rule, ctx->reproject_fma_min_cols,
-                                     ctx->sum_block, (int32_t *)((char *)scratch + search_groups_offset(ctx, N, patch)),
+                                     plan, ctx->reproject_rule, ctx->reproject_fma_min_cols, ctx->sum_block,
+                                     (int32_t *)((char *)scratch + search_groups_offset(ctx, N, patch)),
                                      groups_ready, (hipStream_t)stream),
                     "mh_search_prepared");
 }
@@ -707,7 +603,7 @@ extern "C" int mh_search_prepared(mh_ctx *ctx, const float *points, int N, int p
                                   void *scratch, float *line_ori, float *min_loss, uint8_t *high_conf,
                                   float *best_sample, int32_t *best_rank, int32_t *best_s, void *stream) {
     return search_prepared(ctx, points, N, patch, conf_threshold, nrank, rank_step, ori, base_idx, base_val, scratch, line_ori,
-                           min_loss, high_conf, best_sample, best_rank, best_s, ctx ? ctx->search_variant : 0, 0, stream);
+                           min_loss, high_conf, best_sample, best_rank, best_s, false, 0, stream);
 }
 
 extern "C" int mh_forward(mh_ctx *ctx, const float *points, int N, int patch, float conf_threshold, int nrank, int rank_step,
@@ -742,7 +638,7 @@ extern "C" int mh_forward(mh_ctx *ctx, const float *points, int N, int patch, fl
                           "mh_forward (base-view ranking)"))
         return rc;
     return search_prepared(ctx, points, N, patch, conf_threshold, nrank, rank_step, ori, base_idx, base_val, scratch, line_ori,
-                           min_loss, high_conf, best_sample, best_rank, best_s, 8 /* ordered, classes written */, fuse_groups,
+                           min_loss, high_conf, best_sample, best_rank, best_s, true /* work classes written */, fuse_groups,
                            stream);
 }
 
@@ -1006,7 +902,8 @@ extern "C" int mh_sample_next(mh_ctx *ctx, const float *points, const int32_t *b
     // (the V group sizes of this batch -- stream-ordered work space, so that calls on several streams do not share it)
     int32_t *gcnt = nullptr;
     if (ctx->reproject_rule == 0)
-        MH_HIP(hipMallocAsync((void **)&gcnt, sizeof(int32_t) * (size_t)16 * 16 * ctx->V, (hipStream_t)stream));
+        MH_HIP(hipMallocAsync((void **)&gcnt, sizeof(int32_t) * (size_t)MH_GROUP_COPIES * MH_GROUP_RANKS * ctx->V,
+                              (hipStream_t)stream));
     const int rc = launched(mh_launch_sample_next(ctx->views(), points, base_view, ori, offsets, N, S, samples,
                                                   ctx->reproject_rule, ctx->reproject_fma_min_cols, gcnt,
                                                   (hipStream_t)stream),
@@ -1233,7 +1130,7 @@ static int dog_weights(mh_ctx *ctx, const double *w_lo, int r_lo, const double *
         return fail(MH_ERR_ARG, "mh_dog: kernel radius %d exceeds the built-in limit of %d (sigma <= %.1f at truncate 4); the "
                                 "reference uses sigma 0.4 and 10 (radius 2 and 40)", r_lo > r_hi ? r_lo : r_hi, MH_DG_MAXR,
                     (MH_DG_MAXR + 0.49) / 4.0);
-    MhDogWeightsHost h;
+    MhDogWeights h;
     memset(&h, 0, sizeof h);
     memcpy(h.w[0], w_lo, sizeof(double) * (r_lo + 1));
     memcpy(h.w[1], w_hi, sizeof(double) * (r_hi + 1));
@@ -1241,9 +1138,9 @@ static int dog_weights(mh_ctx *ctx, const double *w_lo, int r_lo, const double *
     h.r[1] = r_hi;
     MH_HIP(hipSetDevice(ctx->device));
     if (!ctx->dog_w) {
-        MH_HIP(hipMalloc(&ctx->dog_w, sizeof(MhDogWeightsHost)));
-        ctx->dog_w_host = new MhDogWeightsHost;
-        memset(ctx->dog_w_host, 0xff, sizeof(MhDogWeightsHost));
+        MH_HIP(hipMalloc(&ctx->dog_w, sizeof(MhDogWeights)));
+        ctx->dog_w_host = new MhDogWeights;
+        memset(ctx->dog_w_host, 0xff, sizeof(MhDogWeights));
     }
     if (memcmp(ctx->dog_w_host, &h, sizeof h) != 0) {
         // (other streams may still be reading the old weights: wait for the device before replacing them)

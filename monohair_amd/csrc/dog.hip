@@ -17,16 +17,10 @@
 // HBM traffic: 1 B/px in, 16 B/px written + read between the passes, 4 (+8) B/px out: ~80 MB per 1080p view.
 #include "mh_device.h"
 
-#define MH_DG_MAXR 48                 // radius limit: sigma <= 11.9 at truncate 4 (the reference uses 0.4 and 10: 2 and 40)
 #define MH_DG_VT_ROWS 32
 #define MH_DG_VT_COLS 64
 #define MH_DG_HZ_ROWS 2
 #define MH_DG_HZ_COLS 128
-
-struct MhDogWeights {                 // device-resident; w[s][j + r[s]] for j = -r[s] .. 0 (the symmetric half incl. the centre)
-    double w[2][MH_DG_MAXR + 1];
-    int r[2];
-};
 
 template <int KIND>                   // 0: uint8 codes (x 1/255), 1: float64 samples
 __global__ __launch_bounds__(256) void mh_dog_vert_kernel(const void *__restrict__ img, int H, int W,

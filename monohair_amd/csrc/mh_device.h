@@ -8,21 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MH_CAM_STRIDE 48
-#define MH_TOPK 20
-#define MH_WAVE 64
+#include "mh_launch.h"   // MhViews, MH_GROUP_COPIES / MH_GROUP_RANKS, MH_CAM_STRIDE / MH_TOPK, the launchers' prototypes
 
-struct MhViews {
-    int V, H, W;
-    const float4 *rec;   // [V][H][W] {ori_row, ori_col, conf, depth}
-    const float *mask;   // [V][H][W]
-    const float *cams;   // [V][MH_CAM_STRIDE]
-    const float4 *tap;   // [V][H][W] {unit ori_row, unit ori_col, clamped conf, 0}: what a patch tap of the search is, per pixel,
-                         // made once at upload by the same mh_unit2 / mh_clampf the front end would apply per iteration
-                         // (nullptr: not resident -- views uploaded as 8-bit codes use the code tables instead)
-    int batch_rule;      // 1: option reproject_rule 0 -- the projections follow the batch (a batch of ONE point projects
-                         // through the single-column form, see mh_cam_project_b); 0: one form for everything
-};
+#define MH_WAVE 64
 
 __device__ __forceinline__ float mh_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
@@ -74,10 +62,7 @@ __device__ __forceinline__ void mh_pixel_of(const float *__restrict__ cam, float
 // MhRule carries what a kernel needs to follow the batch; mode 1 / 2 force the mid / chain forms for every point.
 #define MH_FORM_GEMV 1
 #define MH_FORM_CHAIN 2
-// The counts are kept in MH_GROUP_COPIES partial arrays (a workgroup of the counting kernel adds to copy blockIdx % COPIES):
-// up to 670 points of a 5000-point chunk share one (rank, base view), and that many atomics on ONE address drain in ~9 us.
-#define MH_GROUP_COPIES 16
-#define MH_GROUP_RANKS 16   // = MH_MAX_RANKS of the search
+// (the counts are kept in MH_GROUP_COPIES partial arrays: mh_launch.h)
 struct MhRule {
     const int32_t *gcnt;    // [MH_GROUP_COPIES][MH_GROUP_RANKS][V] partial counts of the points per (rank, base view) of this
                             // batch (nullptr: every group counts as mid-size)

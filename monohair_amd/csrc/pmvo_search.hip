@@ -16,6 +16,7 @@
 // Views in which the point is not visible (vis == -1 => weight 0, PMVO.py:212) are skipped: adding
 // their exact zeros would not change any sum.
 #include "mh_device.h"
+#include "../../include/mh_pmvo_lab.h"   // mh_debug_key_stats
 
 #define MH_MAX_ITEMS 1024
 #define MH_MAX_RANKS 16
@@ -786,9 +787,6 @@ __device__ __forceinline__ void mh_key_block4(unsigned (&ke)[KN], unsigned (&ko)
 #ifndef MH_S3_WAVES
 #define MH_S3_WAVES 5   // waves per SIMD the register allocation aims at (A/B builds: -DMH_S3_WAVES=4|6)
 #endif
-#ifndef MH_PAIR_TAPS
-#define MH_PAIR_TAPS 4    // select-only kernel: two views whose lists hold at most this many taps are evaluated together
-#endif
 #ifndef MH_S3_WAVES_SELECT
 #define MH_S3_WAVES_SELECT MH_S3_WAVES   // the same aim for the select-only kernel (A/B builds: -DMH_S3_WAVES_SELECT=4)
 #endif
@@ -855,16 +853,6 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         const float4 hdr = rec[0];
         const float4 t0 = rec[1];
         float DX[KN], DY[KN], ML[KN], BC[KN];
-#ifdef MH_EXP_NOTAPS   // timing experiments only (wrong results): tools/exp_search_parts.sh
-        ntap = 1;
-#endif
-#ifdef MH_EXP_NOPROJ
-#pragma unroll
-        for (int j = 0; j < KN; ++j) {
-            DX[j] = X0[j] + hdr.z;
-            DY[j] = X1[j] + hdr.w;
-        }
-#else
 #pragma unroll
         for (int jp = 0; jp < KA / 2; ++jp) {
             mh_v2f row, col, dx, dy;
@@ -883,7 +871,6 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
             DX[KA - 1] = dx.x;
             DY[KA - 1] = dy.x;
         }
-#endif
         constexpr int GRP = MH_S3_GRP;
         // the compare-and-select body: exact everywhere (the one body of rounds 1-3; with KEYS the re-evaluation path)
         auto select_body = [&]() {
@@ -1010,76 +997,6 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
             cnt[j] += (w > 0.0f) ? 1 : 0;
         }
     };
-#ifdef MH_EXP_VIEW_PAIRS   // (experiment build only: tools/exp_view_pairs.sh -- measured SLOWER in every form, docs/HISTORY.md round 5)
-    // Two views in flight (select-only kernel, short lists -- the regime of 8-bit maps, ~2 taps per list): there the time of a
-    // view is the dependent chain of its projection (camera record, rcp, sqrt, two refined divisions: 98 of the kernel's 211 us,
-    // 24 for the taps), and five waves per SIMD do not hide it (issue utilisation 0.53).  The projections of TWO visible views
-    // are written as one block of straight-line code, so that the scheduler interleaves the two chains; then the two short tap
-    // loops, then the accumulation in view order -- the same operations on the same values as two calls of one_view.
-    // (The caller pairs views only inside one 16-view block of the cascade: no flush between them.)
-    auto two_views = [&](int va, const float4 *reca, int na, int vb2, const float4 *recb, int nb) {
-        const float *__restrict__ cama = vw.cams + va * MH_CAM_STRIDE;
-        const float *__restrict__ camb = vw.cams + vb2 * MH_CAM_STRIDE;
-        const float4 ha = reca[0], hb = recb[0];
-        const float4 ta = reca[1], tb = recb[1];
-        float DXa[KN], DYa[KN], DXb[KN], DYb[KN];
-#pragma unroll
-        for (int jp = 0; jp < KA / 2; ++jp) {
-            mh_v2f ra, ca, rb, cb, dxa, dya, dxb, dyb;
-            const mh_v2f x0 = mh_v2f{X0[2 * jp], X0[2 * jp + 1]}, x1 = mh_v2f{X1[2 * jp], X1[2 * jp + 1]},
-                         x2 = mh_v2f{X2[2 * jp], X2[2 * jp + 1]};
-            mh_pixel_of_fast2(cama, x0, x1, x2, Hf, Wf, ra, ca);
-            mh_pixel_of_fast2(camb, x0, x1, x2, Hf, Wf, rb, cb);
-            mh_unit2_fast2(ra - mh_splat(ha.z), ca - mh_splat(ha.w), dxa, dya);
-            mh_unit2_fast2(rb - mh_splat(hb.z), cb - mh_splat(hb.w), dxb, dyb);
-            DXa[2 * jp] = dxa.x; DXa[2 * jp + 1] = dxa.y; DYa[2 * jp] = dya.x; DYa[2 * jp + 1] = dya.y;
-            DXb[2 * jp] = dxb.x; DXb[2 * jp + 1] = dxb.y; DYb[2 * jp] = dyb.x; DYb[2 * jp + 1] = dyb.y;
-        }
-        if constexpr (KA & 1) {
-            mh_v2f ra, ca, rb, cb, dxa, dya, dxb, dyb;
-            const mh_v2f x0 = mh_splat(X0[KA - 1]), x1 = mh_splat(X1[KA - 1]), x2 = mh_splat(X2[KA - 1]);
-            mh_pixel_of_fast2(cama, x0, x1, x2, Hf, Wf, ra, ca);
-            mh_pixel_of_fast2(camb, x0, x1, x2, Hf, Wf, rb, cb);
-            mh_unit2_fast2(ra - mh_splat(ha.z), ca - mh_splat(ha.w), dxa, dya);
-            mh_unit2_fast2(rb - mh_splat(hb.z), cb - mh_splat(hb.w), dxb, dyb);
-            DXa[KA - 1] = dxa.x; DYa[KA - 1] = dya.x;
-            DXb[KA - 1] = dxb.x; DYb[KA - 1] = dyb.x;
-        }
-        float MLa[KN], BCa[KN], MLb[KN], BCb[KN];
-        __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-        for (int j = 0; j < KA; ++j) {
-            MLa[j] = mh_one_minus_abs(mh_vadd(mh_vmul(ta.x, DXa[j]), mh_vmul(ta.y, DYa[j])));
-            BCa[j] = ta.z;
-            MLb[j] = mh_one_minus_abs(mh_vadd(mh_vmul(tb.x, DXb[j]), mh_vmul(tb.y, DYb[j])));
-            BCb[j] = tb.z;
-        }
-        for (int t = 1; t < na; ++t) {   // uniform
-            const float4 tp = reca[1 + t];
-            float l[KN];
-#pragma unroll
-            for (int j = 0; j < KA; ++j) l[j] = mh_one_minus_abs(mh_vadd(mh_vmul(tp.x, DXa[j]), mh_vmul(tp.y, DYa[j])));
-            mh_tap_update<KN>(MLa, BCa, l, tp.z);
-        }
-        for (int t = 1; t < nb; ++t) {
-            const float4 tp = recb[1 + t];
-            float l[KN];
-#pragma unroll
-            for (int j = 0; j < KA; ++j) l[j] = mh_one_minus_abs(mh_vadd(mh_vmul(tp.x, DXb[j]), mh_vmul(tp.y, DYb[j])));
-            mh_tap_update<KN>(MLb, BCb, l, tp.z);
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int j = 0; j < KA; ++j) {
-            num[j].a0 = num[j].a0 + MLa[j] * BCa[j];
-            den[j].a0 = den[j].a0 + BCa[j];
-            cnt[j] += (BCa[j] > 0.0f) ? 1 : 0;
-            num[j].a0 = num[j].a0 + MLb[j] * BCb[j];
-            den[j].a0 = den[j].a0 + BCb[j];
-            cnt[j] += (BCb[j] > 0.0f) ? 1 : 0;
-        }
-    };
-#endif
     const int lane = tid & 63, wave = tid >> 6;
     for (int vb = 0; vb < V; vb += 64) {
         const int vv = vb + lane;
@@ -1130,20 +1047,6 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                     flush_upto(vb + b);
                     const int L = __builtin_amdgcn_readlane(len, b);
                     const int off = __builtin_amdgcn_readlane(pre, b) - L - base;
-#ifdef MH_EXP_VIEW_PAIRS
-                    if constexpr (!KEYS) {   // (see two_views)
-                        if (m && L <= MH_PAIR_TAPS + 1) {
-                            const int b2 = (int)__builtin_ctzll(m);
-                            const int L2 = __builtin_amdgcn_readlane(len, b2);
-                            if (L2 <= MH_PAIR_TAPS + 1 && vb + b2 < nf) {
-                                m &= m - 1;
-                                const int off2 = __builtin_amdgcn_readlane(pre, b2) - L2 - base;
-                                two_views(vb + b, s_taps + off, L - 1, vb + b2, s_taps + off2, L2 - 1);
-                                continue;
-                            }
-                        }
-                    }
-#endif
                     one_view(vb + b, s_taps + off, KEYS ? __builtin_amdgcn_readlane(c, b) : L - 1);
                 }
             }
@@ -1695,7 +1598,7 @@ extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank,
                                 const float *base_val, const float4 *taps, int32_t *order /* 2N ints of work space */,
                                 const uint8_t *cnt /* [V,N] list lengths */,
                                 float *line_ori, float *min_loss, uint8_t *high_conf, float *best_sample,
-                                int32_t *best_rank, int32_t *best_s, int variant, int rule_mode, int fma_min_cols,
+                                int32_t *best_rank, int32_t *best_s, MhSearchPlan plan, int rule_mode, int fma_min_cols,
                                 int sum_block, int32_t *gcnt /* MH_GROUP_COPIES * MH_GROUP_RANKS * V ints of work space */,
                                 int groups_ready /* gcnt holds the batch's group sizes already (the fused forward) */,
                                 hipStream_t st) {
@@ -1711,33 +1614,26 @@ extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank,
     if (rule_mode == 0 && !gcnt) return -1;
     const long long cols = (long long)N * S;
     rule.tail_col0 = sum_block ? cols - cols % sum_block : cols;
-    // (variant 9 / 10: the launch split for measurements -- 9 runs what precedes the search (group sizes, work classes, launch
-    // order) and stops, 10 runs mh_search3_kernel alone on what 9 left in the scratch; bench.py times the two with HIP events)
-    const bool select_body = variant >= 100 && variant < 200;
-    if (select_body) variant -= 100;
-    if (variant == 10) groups_ready = 1;
-    if (rule.gcnt && !groups_ready) {
+    const bool portable = plan.portable || !cnt;   // (mh_search3_kernel needs the list lengths)
+    // the group sizes, unless the caller counted them or an earlier PART_PRE_ONLY launch left them in gcnt
+    if (rule.gcnt && !groups_ready && plan.part != MhSearchPlan::PART_KERNEL_ONLY) {
         if (hipMemsetAsync(gcnt, 0, sizeof(int32_t) * (size_t)MH_GROUP_COPIES * MH_GROUP_RANKS * vw.V, st) != hipSuccess) return -1;
         hipLaunchKernelGGL(mh_group_sizes_kernel, dim3((N + 255) / 256, nrank), dim3(256), sizeof(int) * (size_t)vw.V, st,
                            base_idx, N, vw.V, rank_step, gcnt);
     }
-    // variant 0 (default): mh_search3_kernel, workgroups in descending order of work; 7: the same in natural order (A/B);
-    // 1256: the portable mh_search_kernel (cross-check) -- also what runs when the caller has no list lengths
-    // (8: as 0, the work classes are in order[0..N) already -- the fused forward lets the ranking kernel write them)
-    // (+100: the compare-and-select tap body of rounds 1-3 instead of the key body -- 100 / 107 are the A/B and cross-check
-    // forms of 0 / 7)
-    if (variant == 0) variant = cnt ? 6 : 1256;
-    if (variant == 6 || variant == 7 || variant == 8 || variant == 9 || variant == 10) {
-        if (!cnt) return -1;
+    if (!portable) {
+        // the launch order: work classes into order[0..N) unless the caller wrote them, then the points by class into order[N..2N)
         const int32_t *ord = nullptr;
-        if (variant != 7 && order && N > 1) {
-            if (variant == 6 || variant == 9)
-                hipLaunchKernelGGL(mh_search_work_kernel, dim3((N + 3) / 4), dim3(256), 0, st, cnt, vw.V, N, P1, base_val,
-                                   nrank, rank_step, S, 256, order, (int)(rule.tail_col0 / S));
-            if (variant != 10) hipLaunchKernelGGL(mh_search_order_kernel, dim3(1), dim3(1024), 0, st, N, order);
+        if (plan.order != MhSearchPlan::ORDER_NATURAL && order && N > 1) {
+            if (plan.part != MhSearchPlan::PART_KERNEL_ONLY) {
+                if (plan.order == MhSearchPlan::ORDER_BY_WORK)
+                    hipLaunchKernelGGL(mh_search_work_kernel, dim3((N + 3) / 4), dim3(256), 0, st, cnt, vw.V, N, P1, base_val,
+                                       nrank, rank_step, S, 256, order, (int)(rule.tail_col0 / S));
+                hipLaunchKernelGGL(mh_search_order_kernel, dim3(1), dim3(1024), 0, st, N, order);
+            }
             ord = order + N;
         }
-        if (variant == 9) return (int)hipGetLastError();
+        if (plan.part == MhSearchPlan::PART_PRE_ONLY) return (int)hipGetLastError();
 #define MH_S3_LAUNCH(BIG, KEYS, BIGP)                                                                                   \
     hipLaunchKernelGGL((mh_search3_kernel<256, BIG, KEYS, BIGP>), dim3(N), dim3(256), 0, st, vw, offs, S, nrank, rank_step, \
                        pts, N, P1, thr, ori_c, base_idx, base_val, taps, cnt, ord, line_ori, min_loss, high_conf,       \
@@ -1746,21 +1642,19 @@ extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank,
         // for longer lists two more)
         const bool bigp = P1 - 1 > 64;
         if (vw.V > 256) {
-            if (select_body) MH_S3_LAUNCH(true, false, false);
+            if (plan.select_body) MH_S3_LAUNCH(true, false, false);
             else if (bigp) MH_S3_LAUNCH(true, true, true);
             else MH_S3_LAUNCH(true, true, false);
         } else {
-            if (select_body) MH_S3_LAUNCH(false, false, false);
+            if (plan.select_body) MH_S3_LAUNCH(false, false, false);
             else if (bigp) MH_S3_LAUNCH(false, true, true);
             else MH_S3_LAUNCH(false, true, false);
         }
 #undef MH_S3_LAUNCH
-    } else if (variant == 1256) {
+    } else {
         hipLaunchKernelGGL((mh_search_kernel<4, 256>), dim3(N), dim3(256), 0, st, vw, offs, S, nrank, rank_step, pts, N, P1,
                            thr, ori_c, base_idx, base_val, taps, line_ori, min_loss, high_conf, best_sample, best_rank,
                            best_s, rule);
-    } else {
-        return -1;
     }
     return (int)hipGetLastError();
 }

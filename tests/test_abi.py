@@ -15,6 +15,42 @@ def declared_symbols(headers=("mh_pmvo.h", "mh_pmvo_lab.h")):
     return sorted(out)
 
 
+def declared_prototypes(headers=("mh_pmvo.h", "mh_pmvo_lab.h")):
+    """{name: (return type, [parameter types])} of every prototype, each type reduced to its class: "pointer", "char*"
+    (const char *), "void" or the scalar type's own name."""
+    def kind(decl, named):
+        decl = " ".join(decl.replace("*", " * ").split())
+        if "*" in decl:
+            return "char*" if decl.startswith("const char *") and decl.count("*") == 1 else "pointer"
+        words = [w for w in decl.split() if w != "const"]
+        if named and len(words) > 1:
+            words = words[:-1]       # the parameter's name
+        return " ".join(words)
+
+    out = {}
+    for h in headers:
+        hdr = open(os.path.join(ROOT, "include", h)).read()
+        hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+        hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+        for ret, name, params in re.findall(r"([^;{}()]*?)\b(mh_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr):
+            params = [] if params.strip() in ("", "void") else [kind(q, True) for q in params.split(",")]
+            assert name not in out, name
+            out[name] = (kind(ret, False), params)
+    return out
+
+
+def bound_kind(t):
+    """the class of a ctypes type in the terms of declared_prototypes"""
+    if t is None:
+        return "void"
+    if t is ctypes.c_char_p:
+        return "char*"
+    if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_longlong: "long long",
+            ctypes.c_size_t: "size_t"}[t]
+
+
 def test_lab_switches_are_not_in_the_supported_header():
     """include/mh_pmvo.h is what an integrator binds; the A/B forms and cross-check kernels live in mh_pmvo_lab.h"""
     main, lab = set(declared_symbols(("mh_pmvo.h",))), set(declared_symbols(("mh_pmvo_lab.h",)))
@@ -28,6 +64,11 @@ def test_header_declares_the_bound_entry_points():
     from monohair_amd import _lib
 
     assert set(_lib.EXPORTS) == set(declared_symbols())
+    # ... with the types the headers give them: the ctypes table is a hand-written copy of the prototypes
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols()
+    bound = {name: (bound_kind(res), [bound_kind(a) for a in args]) for name, (res, args) in _lib._SIGS.items()}
+    assert {n: (protos[n], bound[n]) for n in protos if protos[n] != bound[n]} == {}
 
 
 def test_library_loads_and_exports_everything():
