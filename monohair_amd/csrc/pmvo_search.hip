@@ -12,7 +12,8 @@
 // and first tap: scalar loads; the rest: broadcast vector loads, what the backend selects for the ping-pong
 // groups) and the inner loop is pure VALU: per (item, tap) 2 mul + add + (1-|x|) + cmp + 2 cndmask in the portable kernel and
 // the select body of the shipped one; its key body keeps the running (loss, tap) minimum as one integer key per item and
-// needs 2 mul + add + sub + lshl_or + half a min3 (see mh_tap_key).
+// needs 2 mul + add + sub + lshl_or + half a min3 (see mh_tap_key); a list's last tap seeds the minimum instead of padding
+// a four-tap block (see mh_key_walked).
 // Views in which the point is not visible (vis == -1 => weight 0, PMVO.py:212) are skipped: adding
 // their exact zeros would not change any sum.
 #include "mh_device.h"
@@ -476,7 +477,26 @@ __device__ __forceinline__ void mh_tap_update(float (&ML)[KA], float (&BC)[KA], 
 #ifndef MH_KEY_MIN_TAPS
 #define MH_KEY_MIN_TAPS 10           // lists up to this length go through the select body directly
 #endif
-#define MH_KEY_PAD 4                 // lists are padded in LDS to a multiple of this many taps with (0, 0): cs = 0, t' = C
+#define MH_KEY_PAD 4                 // the key block takes this many taps; (0, 0) records fill a last block: cs = 0, t' = C
+// How many taps of a list of c > MH_KEY_MIN_TAPS taps the key blocks walk, and how many tap records the list takes in LDS.
+// Padded to whole blocks, a complete 7 x 7 patch (49 taps: 85 % of the bench scene's lists) ran a thirteenth block for one
+// tap.  The LAST tap of a list does not need a block: its key is the initial value of the accumulator of its parity (a key
+// carries its place, so the order in which it enters the minimum does not matter) -- 5 instructions per item + 2 selects
+// in place of the two initialising moves, against the 22 per item of a block.  The blocks walk the c - 1 taps in front of it,
+// padded to whole blocks -- always, without a branch on c & 3: one block less for c = 1 mod 4, the same blocks otherwise;
+// where the padding reaches the last tap (c = 2, 3 mod 4) that tap is evaluated twice, to the same key.  (Seeding the last
+// TWO taps, one even and one odd, needs no select and also saves the block of c = 2 mod 4, for 8 instead of 5 more
+// instructions per item on every other list: the same speed on the bench scene within the noise, not kept.)  Lists of
+// more than one 64-tap group (BIGP: patch 9 and 11) stay padded.
+template <bool BIGP>
+__device__ __forceinline__ int mh_key_walked(int c) {
+    return (c - (BIGP ? 0 : 1) + MH_KEY_PAD - 1) & ~(MH_KEY_PAD - 1);
+}
+template <bool BIGP>
+__device__ __forceinline__ int mh_key_staged(int c) {
+    const int w = mh_key_walked<BIGP>(c);
+    return w > c ? w : c;
+}
 // (wave, view) visits of the key body: [0] all, [1] one-tap / short / NaN-seed lists (select body directly), [2] evaluated
 // again with the select body after the key body.  [2] is always counted -- one atomic in a branch the bench scene takes 0 times
 // in 95 M -- so that a test can assert that it was inside that branch (tests/test_key_reeval_gpu.py); [0] and [1] sit in the
@@ -911,14 +931,14 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         if constexpr (!KEYS) {
             select_body();
         } else {
-            // the key body (see mh_tap_key): taps in groups of 64, the list padded to a multiple of MH_KEY_PAD taps
+            // the key body (see mh_tap_key): taps in groups of 64, blocks of MH_KEY_PAD taps (see mh_key_walked)
             // uniform: a short list (the key body's fixed cost per view -- padding, decode -- only pays from about a dozen
             // taps on: lists of 8-bit maps are mostly shorter, lists of continuous maps hardly ever) / a NaN seed tap
             bool again = (ntap <= MH_KEY_MIN_TAPS) || !(t0.x == t0.x && t0.y == t0.y);
             MH_KEY_COUNT(0);
             if (again) MH_KEY_COUNT(1);
             if (!again) {
-                const int ntp = (ntap + MH_KEY_PAD - 1) & ~(MH_KEY_PAD - 1);
+                const int ntp = mh_key_walked<BIGP>(ntap);
                 // even taps of a 64-tap group into ke, odd taps into ko, the key's index = the tap's place among them
                 unsigned ke[KN], ko[KN];
                 const unsigned rec1 = (unsigned)(size_t)(const __attribute__((address_space(3))) float4 *)(rec + 1);
@@ -930,11 +950,24 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                 // taps [ta, tb) of one 64-tap group: (tx, ty) of tap i is the first half of record 1 + i
                 auto group = [&](int ta, int tb) {
                     const float2 *__restrict__ t2 = reinterpret_cast<const float2 *>(rec + 1);
-#pragma unroll
-                    for (int j = 0; j < KN; ++j) ke[j] = ko[j] = 0xFFFFFFFFu;
                     float2 ga[GRP], gb[GRP];
 #pragma unroll
                     for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * (ta + u)];
+                    if constexpr (BIGP || KM == 0) {
+#pragma unroll
+                        for (int j = 0; j < KN; ++j) ke[j] = ko[j] = 0xFFFFFFFFu;
+                    } else {
+                        // the list's last tap seeds the accumulator of its parity (uniform), the other one starts empty
+                        const int is = ntap - 1;
+                        const float2 ts = t2[2 * is];
+                        const bool even = (is & 1) == 0;
+#pragma unroll
+                        for (int j = 0; j < KM; ++j) {
+                            const unsigned k = mh_tap_key(mh_vadd(mh_vmul(ts.x, DX[j]), mh_vmul(ts.y, DY[j])), is >> 1);
+                            ke[j] = even ? k : 0xFFFFFFFFu;
+                            ko[j] = even ? 0xFFFFFFFFu : k;
+                        }
+                    }
                     for (int t = ta; t < tb;) {
 #pragma unroll
                         for (int u = 0; u < GRP; ++u) gb[u] = t2[2 * (t + GRP + u)];
@@ -1003,9 +1036,9 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         // list length of view vv (0: the view does not see the point); the first block's was requested in the kernel's
         // prologue, in front of the first barrier
         const int c = vb == 0 ? c_first : ((vv < V) ? (int)vcnt[(size_t)vv * N + n] : 0);
-        // records: header + taps (KEYS: the taps of a list that goes through the key body padded to a multiple of
-        // MH_KEY_PAD with neutral (0, 0) records)
-        const int len = c ? ((KEYS && c > MH_KEY_MIN_TAPS) ? ((c + MH_KEY_PAD - 1) & ~(MH_KEY_PAD - 1)) : c) + 1 : 0;
+        // records: header + taps (KEYS: behind the taps of a list that goes through the key body, the neutral (0, 0) records
+        // that fill its last block -- mh_key_staged)
+        const int len = c ? ((KEYS && c > MH_KEY_MIN_TAPS) ? mh_key_staged<BIGP>(c) : c) + 1 : 0;
         int pre = len;                                               // inclusive prefix sum over the lanes
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
