@@ -408,6 +408,35 @@ int mh_occ_check(mh_ctx *ctx, const double *pts, const long long *offsets, int n
                  void *stream);
 int mh_smooth_strands(mh_ctx *ctx, double *pts, const long long *offsets, int n, double lap_constraint,
                       double pos_constraint, double *work, void *stream);
+/* Scalp attachment (HairGrowing.connect_to_scalp, HairGrow.py:606-784 with compute_strands_similar :788-812, connect_strands
+ * :384-416 and random_move_strands, Utils/PMVO_utils.py:618-658): ONE pass of its while loop; thresholds and termination
+ * stay with the caller.  Strands are one float32 point list pts [P,3] in voxel units with offsets [n+1] (int64); flags [n]:
+ * bit 0 rooted, bit 1 out.  The core points core [n_core,3] are the points of the strands rooted when the pass starts, in
+ * strand order, with core_strand [n_core] (the strand of each) and core_rank [n_core]: rank[KDTree(core).indices[j]] = j,
+ * the order in which query_ball_point returns its members.  order / cell_start: mh_grid_build's binning of core on the
+ * grid (host arrays grid = {origin xyz, cell size > thr_dist}, dims).  active [n_active]: the strands neither rooted nor
+ * out.  Every other pointer is on the device.
+ * mh_scalp_ball_count: count[a] = members of query_ball_point(strand[0], thr_dist) (float64, bound included).
+ * mh_scalp_choose: ball_offsets = exclusive scan of count [n_active+1], ball_scratch one 64-bit word per member.  Per
+ *   active strand i: flip[i] = 1 if the flip test reverses it, best_strand[i] / best_index[i] = the neighbour and the point
+ *   index it joins (-1: none).  The caller presets the three arrays for the strands that are not active (0, -1, 0).
+ * mh_scalp_emit: new_offsets = exclusive scan of the new lengths (len + best_index + 1 where joined).  Writes every strand
+ *   to new_pts (reversed where flip is set, the join in front); a joined strand goes through random_move_strands' test on
+ *   vox [Z,H,W,4] = {orientation with y/z negated, occupancy} (mh_volume_pack): flags, out_ratio [n] (float64) and similar
+ *   [n] are updated for it, counters[0..2] += newly rooted, newly out, strands torch's indexing would refuse. */
+int mh_scalp_ball_count(mh_ctx *ctx, const float *pts, const long long *offsets, const int32_t *active, int n_active,
+                        const float *core, int n_core, const int32_t *order, const int32_t *cell_start, const float *grid,
+                        const int32_t *dims, double thr_dist, long long *count, void *stream);
+int mh_scalp_choose(mh_ctx *ctx, const float *pts, const long long *offsets, const int32_t *active, int n_active,
+                    const float *core, const int32_t *core_strand, const int32_t *core_rank, int n_core,
+                    const int32_t *order, const int32_t *cell_start, const float *grid, const int32_t *dims,
+                    double thr_dist, double thr_dot, const double *out_ratio, const long long *ball_offsets,
+                    unsigned long long *ball_scratch, uint8_t *flip, int32_t *best_strand, int32_t *best_index,
+                    void *stream);
+int mh_scalp_emit(mh_ctx *ctx, const float *pts, const long long *offsets, int n, const uint8_t *flip,
+                  const int32_t *best_strand, const int32_t *best_index, const long long *new_offsets, const float *vox,
+                  int W, int H, int Z, double out_ratio_threshold, float *new_pts, uint8_t *flags, double *out_ratio,
+                  float *similar, int32_t *counters, void *stream);
 
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of

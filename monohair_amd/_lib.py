@@ -64,6 +64,10 @@ _SIGS = {
     "mh_occ_check": (ci, [vp, vp, vp, ci, vp, cll, ci, ci, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, vp, vp]),
     "mh_smooth_strands": (ci, [vp, vp, vp, ci, ctypes.c_double, ctypes.c_double, vp, vp]),
+    "mh_scalp_ball_count": (ci, [vp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, ctypes.c_double, vp, vp]),
+    "mh_scalp_choose": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp,
+                             vp, vp, vp, vp, vp]),
+    "mh_scalp_emit": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.c_double, vp, vp, vp, vp, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

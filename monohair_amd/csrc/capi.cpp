@@ -1076,6 +1076,57 @@ extern "C" int mh_smooth_strands(mh_ctx *ctx, double *pts, const long long *offs
                     "mh_smooth_strands");
 }
 
+// ---- scalp attachment (HairGrow.py:606-812): one pass of connect_to_scalp's while loop ---------------------------------
+static bool scalp_grid_ok(const float *grid, const int32_t *dims) {
+    return grid && dims && grid[3] > 0.0f && dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 &&
+           (long long)dims[0] * dims[1] * dims[2] < (1ll << 31);
+}
+
+extern "C" int mh_scalp_ball_count(mh_ctx *ctx, const float *pts, const long long *offsets, const int32_t *active,
+                                   int n_active, const float *core, int n_core, const int32_t *order,
+                                   const int32_t *cell_start, const float *grid, const int32_t *dims, double thr_dist,
+                                   long long *count, void *stream) {
+    if (n_active == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !active || !core || !order || !cell_start || !count || n_active < 0 || n_core < 1 ||
+        !scalp_grid_ok(grid, dims) || !(thr_dist > 0.0) || !((double)grid[3] > thr_dist))
+        return fail(MH_ERR_ARG, "mh_scalp_ball_count: bad arguments");
+    return launched(mh_launch_scalp_ball_count(pts, (const int64_t *)offsets, active, n_active, core, order, cell_start,
+                                               grid, dims, thr_dist, (int64_t *)count, (hipStream_t)stream),
+                    "mh_scalp_ball_count");
+}
+
+extern "C" int mh_scalp_choose(mh_ctx *ctx, const float *pts, const long long *offsets, const int32_t *active, int n_active,
+                               const float *core, const int32_t *core_strand, const int32_t *core_rank, int n_core,
+                               const int32_t *order, const int32_t *cell_start, const float *grid, const int32_t *dims,
+                               double thr_dist, double thr_dot, const double *out_ratio, const long long *ball_offsets,
+                               unsigned long long *ball_scratch, uint8_t *flip, int32_t *best_strand, int32_t *best_index,
+                               void *stream) {
+    if (n_active == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !active || !core || !core_strand || !core_rank || !order || !cell_start ||
+        !out_ratio || !ball_offsets || !ball_scratch || !flip || !best_strand || !best_index || n_active < 0 ||
+        n_core < 1 || !scalp_grid_ok(grid, dims) || !(thr_dist > 0.0) || !((double)grid[3] > thr_dist))
+        return fail(MH_ERR_ARG, "mh_scalp_choose: bad arguments");
+    return launched(mh_launch_scalp_choose(pts, (const int64_t *)offsets, active, n_active, core, core_strand, core_rank,
+                                           order, cell_start, grid, dims, thr_dist, thr_dot, out_ratio,
+                                           (const int64_t *)ball_offsets, ball_scratch, flip, best_strand, best_index,
+                                           (hipStream_t)stream),
+                    "mh_scalp_choose");
+}
+
+extern "C" int mh_scalp_emit(mh_ctx *ctx, const float *pts, const long long *offsets, int n, const uint8_t *flip,
+                             const int32_t *best_strand, const int32_t *best_index, const long long *new_offsets,
+                             const float *vox, int W, int H, int Z, double out_ratio_threshold, float *new_pts,
+                             uint8_t *flags, double *out_ratio, float *similar, int32_t *counters, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !pts || !offsets || !flip || !best_strand || !best_index || !new_offsets || !vox || !new_pts || !flags ||
+        !out_ratio || !similar || !counters || n < 0 || W < 1 || H < 1 || Z < 1)
+        return fail(MH_ERR_ARG, "mh_scalp_emit: bad arguments");
+    return launched(mh_launch_scalp_emit(pts, (const int64_t *)offsets, n, flip, best_strand, best_index,
+                                         (const int64_t *)new_offsets, (const float4 *)vox, W, H, Z, out_ratio_threshold,
+                                         new_pts, flags, out_ratio, similar, counters, (hipStream_t)stream),
+                    "mh_scalp_emit");
+}
+
 static int gabor_alloc(mh_ctx *ctx) {
     if (ctx->gabor) return MH_OK;
     MH_HIP(hipSetDevice(ctx->device));

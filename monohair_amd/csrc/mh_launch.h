@@ -209,4 +209,18 @@ int mh_launch_chain_emit(const double *P, const int64_t *offs, int N, const int3
 int mh_launch_occ_check(const double *S, const int64_t *offs, int N, const float *occ, int64_t ostride, int W, int H, int Z,
                         double vx, double vy, double vz, double vs, int32_t *status, hipStream_t st);
 int mh_launch_smooth(double *S, const int64_t *offs, int N, double lap, double pos, double *work, hipStream_t st);
+
+// ---- hairscalp.hip (loads with its first launch, like hairconnect.hip)
+int mh_launch_scalp_ball_count(const float *P, const int64_t *offs, const int32_t *act, int nact, const float *core,
+                               const int32_t *order, const int32_t *cstart, const float *grid, const int32_t *dims,
+                               double thr_dist, int64_t *count, hipStream_t st);
+int mh_launch_scalp_choose(const float *P, const int64_t *offs, const int32_t *act, int nact, const float *core,
+                           const int32_t *csid, const int32_t *crank, const int32_t *order, const int32_t *cstart,
+                           const float *grid, const int32_t *dims, double thr_dist, double thr_dot, const double *out_ratio,
+                           const int64_t *boff, unsigned long long *bscr, uint8_t *flip, int32_t *best_sid,
+                           int32_t *best_idx, hipStream_t st);
+int mh_launch_scalp_emit(const float *P, const int64_t *offs, int n, const uint8_t *flip, const int32_t *best_sid,
+                         const int32_t *best_idx, const int64_t *noffs, const float4 *vox, int W, int H, int Z,
+                         double ratio_thr, float *Pn, uint8_t *flags, double *out_ratio, float *similar, int32_t *counters,
+                         hipStream_t st);
 }

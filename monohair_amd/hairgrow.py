@@ -2,8 +2,9 @@
 reference's `HairGrow.py::class HairGrowing` (__init__ :41-55, trace :59-149, traceFromScalp :154-223,
 GenerateGuideStrandFromScalp :226-265, randomlyGenerateSegments :269-299, VoxelToWorld :816-824), the immediate
 consumer of Ori3D.mat / Occ3D.mat, and the segment connection that follows it
-(find_connect_info :434-590 with connect_segments :303-420, the connect_segments stage of __main__ :925-952).  Scalp
-attachment (connect_scalp, HairGrow.py:593-786) is not part of this package.
+(find_connect_info :434-590 with connect_segments :303-420, the connect_segments stage of __main__ :925-952), and the
+scalp attachment that ends the pipeline (connect_to_scalp :606-812, WorldToVoxel :826-835, the connect_scalp stage of
+__main__ :954-976, csrc/hairscalp.hip).
 
 All seeds are traced in parallel by the HIP kernels of csrc/hairgrow.hip; the sequential `flag` gate only decides
 which finished traces are kept and is replayed afterwards (mh_strands_accept).  The jitter of every trace() call
@@ -16,7 +17,7 @@ import torch
 
 from . import _lib
 from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
-                         save_hair_strands, voxel_to_points)
+                         points_to_voxel, save_hair_strands, voxel_to_points)
 from .strand_smooth import smooth_strands
 
 _KNN_K = 50                                                      # k of the reference's end queries
@@ -303,6 +304,144 @@ class HairGrowing:
         self.connect_fail = fail
         return new_strands
 
+    def connect_to_scalp(self, strands, num_root, out_ratio, infer_inner=False):
+        """HairGrow.py:606-784: attaches the floating strands (strands[num_root:], float32 [L,3] in voxel units, L >= 2) to
+        strands that are rooted, pass after pass, and returns the rooted and the "out" strands in index order.  out_ratio:
+        the reference's args.HairGenerate.out_ratio (the occupied fraction a join must exceed).  infer_inner only selects
+        the same thresholds again in the reference.  Each pass is three kernels over all floating strands
+        (csrc/hairscalp.hip); the host builds ONE scipy KDTree per change of the rooted set, for the order in which
+        query_ball_point returns its members, and reads three counters per pass.  Left behind: self.scalp_passes (per
+        pass: thr_dist, thr_dot, rooted and out counts after it), self.scalp_root_flag / scalp_out_flag /
+        scalp_out_ratio / scalp_flips (times reversed) / scalp_choice ([n,2]: last neighbour and point index joined, -1
+        none) / scalp_similar (random_move_strands' orientation score of that join)."""
+        from scipy.spatial import KDTree
+
+        n = len(strands)
+        arrs = [np.ascontiguousarray(s, dtype=np.float32) for s in strands]
+        if any(a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 2 for a in arrs):
+            raise _lib.MhError("connect_to_scalp: every strand must be [L,3] with L >= 2")
+        num_root = int(num_root)
+        if n == 0 or num_root <= 0:
+            raise _lib.MhError("connect_to_scalp: no rooted strand (the reference's np.concatenate of an empty core list "
+                               "raises here)")
+        dev, L, ctx = self.device, _lib.lib(), self._ctx
+        lens = np.array([a.shape[0] for a in arrs], np.int64)
+        offs_h = np.zeros(n + 1, np.int64)
+        np.cumsum(lens, out=offs_h[1:])
+        pts_h = np.concatenate(arrs, 0)
+        if not np.isfinite(pts_h).all():
+            raise _lib.MhError("connect_to_scalp: non-finite strand points")
+        flags_h = np.zeros(n, np.uint8)
+        flags_h[:num_root] = 1
+        P = torch.from_numpy(pts_h).to(dev)
+        offs = torch.from_numpy(offs_h).to(dev)
+        flags = torch.from_numpy(flags_h).to(dev)
+        oratio = torch.zeros(n, dtype=torch.float64, device=dev)
+        similar = torch.zeros(n, dtype=torch.float32, device=dev)
+        flips = torch.zeros(n, dtype=torch.int32, device=dev)
+        choice = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+        counters = torch.zeros(3, dtype=torch.int32, device=dev)
+        thr_dist, thr_dot, max_thr_dist, max_dot_dist = 0.5, 0.9, 2.0, 0.6
+        rooted, out_n = num_root, 0
+        self.scalp_passes = []
+        core = None           # rebuilt when the rooted set has changed
+        with torch.cuda.device(dev):
+            while True:
+                act = torch.nonzero(flags == 0)[:, 0].to(torch.int32)
+                nact = int(act.shape[0])
+                new_root = new_out = 0
+                if nact:
+                    if core is None:
+                        pid = torch.repeat_interleave(torch.arange(n, device=dev), offs[1:] - offs[:-1])
+                        sel = (flags[pid] & 1) != 0
+                        core = P[sel].contiguous()
+                        csid = pid[sel].to(torch.int32)
+                        core_h = core.cpu().numpy()
+                        M = core_h.shape[0]
+                        rank_h = np.empty(M, np.int32)
+                        rank_h[KDTree(core_h).indices] = np.arange(M, dtype=np.int32)
+                        crank = torch.from_numpy(rank_h).to(dev)
+                        lo, hi = core_h.min(0), core_h.max(0)
+                        scratch = torch.empty(int(L.mh_grid_scratch_bytes(M)), dtype=torch.uint8, device=dev)
+                        order = torch.empty(M, dtype=torch.int32, device=dev)
+                        grid_thr = None
+                    if grid_thr != thr_dist:
+                        # cells a little larger than the radius (the cell of a point is a float32 floor), coarsened
+                        # while there would be more than max(4M, 2^20) of them
+                        h = thr_dist * 1.01
+                        while True:
+                            dims = np.floor((hi - lo).astype(np.float64) / h).astype(np.int64) + 1
+                            if int(np.prod(dims)) <= max(4 * M, 1 << 20):
+                                break
+                            h *= 2.0
+                        grid = np.array([lo[0], lo[1], lo[2], h], np.float32)
+                        dims = dims.astype(np.int32)
+                        cstart = torch.empty(int(np.prod(dims)) + 1, dtype=torch.int32, device=dev)
+                        _lib.check(L.mh_grid_build(ctx, _hp(grid), _hp(dims), _lib.ptr(core), M, _lib.ptr(scratch),
+                                                   scratch.numel(), None, _lib.ptr(order), _lib.ptr(cstart), None,
+                                                   _lib.stream_ptr()), "mh_grid_build")
+                        grid_thr = thr_dist
+                    bcnt = torch.empty(nact, dtype=torch.int64, device=dev)
+                    _lib.check(L.mh_scalp_ball_count(ctx, _lib.ptr(P), _lib.ptr(offs), _lib.ptr(act), nact, _lib.ptr(core),
+                                                     M, _lib.ptr(order), _lib.ptr(cstart), _hp(grid), _hp(dims), thr_dist,
+                                                     _lib.ptr(bcnt), _lib.stream_ptr()), "mh_scalp_ball_count")
+                    boff = torch.zeros(nact + 1, dtype=torch.int64, device=dev)
+                    torch.cumsum(bcnt, 0, out=boff[1:])
+                    bscr = torch.empty(max(int(boff[-1]), 1), dtype=torch.int64, device=dev)
+                    flip = torch.zeros(n, dtype=torch.uint8, device=dev)
+                    bsid = torch.full((n,), -1, dtype=torch.int32, device=dev)
+                    bidx = torch.zeros(n, dtype=torch.int32, device=dev)
+                    _lib.check(L.mh_scalp_choose(ctx, _lib.ptr(P), _lib.ptr(offs), _lib.ptr(act), nact, _lib.ptr(core),
+                                                 _lib.ptr(csid), _lib.ptr(crank), M, _lib.ptr(order), _lib.ptr(cstart),
+                                                 _hp(grid), _hp(dims), thr_dist, thr_dot, _lib.ptr(oratio), _lib.ptr(boff),
+                                                 _lib.ptr(bscr), _lib.ptr(flip), _lib.ptr(bsid), _lib.ptr(bidx),
+                                                 _lib.stream_ptr()), "mh_scalp_choose")
+                    joined = bsid >= 0
+                    newlen = (offs[1:] - offs[:-1]) + torch.where(joined, bidx.long() + 1, torch.zeros_like(bidx).long())
+                    noffs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+                    torch.cumsum(newlen, 0, out=noffs[1:])
+                    Pn = torch.empty((int(noffs[-1]), 3), dtype=torch.float32, device=dev)
+                    counters.zero_()
+                    _lib.check(L.mh_scalp_emit(ctx, _lib.ptr(P), _lib.ptr(offs), n, _lib.ptr(flip), _lib.ptr(bsid),
+                                               _lib.ptr(bidx), _lib.ptr(noffs), _lib.ptr(self._vox), self.W, self.H, self.Z,
+                                               float(out_ratio), _lib.ptr(Pn), _lib.ptr(flags), _lib.ptr(oratio),
+                                               _lib.ptr(similar), _lib.ptr(counters), _lib.stream_ptr()), "mh_scalp_emit")
+                    new_root, new_out, refused = (int(c) for c in counters.cpu())
+                    if refused:
+                        raise _lib.MhError("connect_to_scalp: a joined strand indexes outside the occupancy volume (the "
+                                           "reference's torch indexing raises IndexError here)")
+                    flips += flip
+                    choice[joined] = torch.stack([bsid, bidx], 1)[joined]
+                    P, offs = Pn, noffs
+                    if new_root:
+                        core = None
+                rooted += new_root
+                out_n += new_out
+                self.scalp_passes.append((thr_dist, thr_dot, rooted, out_n))
+                if not new_root > (n - num_root) // 500:
+                    if thr_dist == max_thr_dist and thr_dot == max_dot_dist:
+                        break
+                    thr_dist = min(thr_dist + 0.25, max_thr_dist)
+                    thr_dot = max(thr_dot - 0.075, max_dot_dist)
+            flags_h = flags.cpu().numpy()
+            pts_h, offs_h = P.cpu().numpy(), offs.cpu().numpy()
+            self.scalp_out_ratio = oratio.cpu().numpy()
+            self.scalp_similar = similar.cpu().numpy()
+            self.scalp_flips = flips.cpu().numpy()
+            self.scalp_choice = choice.cpu().numpy()
+        self.scalp_root_flag, self.scalp_out_flag = (flags_h & 1) != 0, (flags_h & 2) != 0
+        return [pts_h[offs_h[i]:offs_h[i + 1]] for i in np.flatnonzero(flags_h)]
+
+    def WorldToVoxel(self, strands, bust_to_origin=None):
+        """HairGrow.py:826-835 -> list of float32 [L,3] arrays in voxel units (adds bust_to_origin to the caller's arrays
+        in place, like the reference)."""
+        out = []
+        for ss in strands:
+            if bust_to_origin is not None:
+                ss += bust_to_origin
+            out.append(points_to_voxel(torch.from_numpy(np.asarray(ss)).type(torch.float).clone()).numpy())
+        return out
+
     def VoxelToWorld(self, strands, bust_to_origin=None):
         """HairGrow.py:816-824."""
         out = []
@@ -358,3 +497,27 @@ def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect
     new_strands = smooth_strands(new_strands, 4.0, 2.0, device=device)
     save_hair_strands(os.path.join(save_path, "strands.hair"), new_strands, bust, translate=False)
     return new_strands, solver
+
+
+def connect_scalp(save_path, bust_to_origin, out_ratio, occ_path=None, ori_path=None, device="cuda:0", occ=None, ori=None,
+                  infer_inner=False):
+    """The `connect_scalp` stage of HairGrow.py's __main__ (:954-976): reads strands.hair and num_root.npy from save_path,
+    attaches the floating strands in voxel space (HairGrowing.connect_to_scalp on the volume of occ_path / ori_path or the
+    arrays occ / ori), returns to world units, smooths every strand (4.0, 2.0) and writes connected_strands.hair.
+    out_ratio: the case's HairGenerate.out_ratio.  Returns (strands, solver)."""
+    import os
+
+    segment, points = load_strand(os.path.join(save_path, "strands.hair"))
+    num_root = int(np.load(os.path.join(save_path, "num_root.npy")))
+    bust = np.asarray(bust_to_origin, dtype=np.float64)
+    strands = np.split(points, np.cumsum(segment)[:-1]) if len(segment) else []
+    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
+    connected = solver.connect_to_scalp(solver.WorldToVoxel(strands, bust), num_root, out_ratio, infer_inner)
+    world = []
+    for ss in connected:
+        w = voxel_to_points(torch.from_numpy(ss.copy())).numpy()
+        w -= bust
+        world.append(w)
+    world = smooth_strands(world, 4.0, 2.0, device=device)
+    save_hair_strands(os.path.join(save_path, "connected_strands.hair"), world, bust, translate=False)
+    return world, solver
