@@ -438,6 +438,21 @@ int mh_scalp_emit(mh_ctx *ctx, const float *pts, const long long *offsets, int n
                   int W, int H, int Z, double out_ratio_threshold, float *new_pts, uint8_t *flags, double *out_ratio,
                   float *similar, int32_t *counters, void *stream);
 
+/* Scalp sampling (HairGrow.py:880-897: Open3D's sample_points_uniformly with interpolated vertex normals, then the step
+ * to voxel space), float64.  vertices / normals [nv,3] float64, faces [nf,3] int32 with every index in [0, nv): the caller
+ * checks them, the kernels do not.
+ * mh_tri_area64: area[t] = 0.5 * |(b-a) x (c-a)|.
+ * mh_mesh_sample: bounds [nf] (int64, non-decreasing, bounds[nf-1] = n): sample i lies in the first triangle t with
+ *   bounds[t] > i -- Open3D's allocation, bounds[t] = round(n * cdf[t]).  uniforms [n,2] in [0,1).  With r1 = sqrt(u0),
+ *   r2 = u1 the weights (1-r1, r1(1-r2), r1 r2) on (a, b, c) give the point and the normal.  out_points = ((p +
+ *   bust_to_origin) * (1,-1,-1) - vmin) / 0.0025 with vmin the float32 (-0.32, -0.32, -0.24) widened; out_normals = the
+ *   normal over its 2-norm, y/z negated; both cast to float32 [n,3].  bust_to_origin: HOST [3].  out_triangle (optional,
+ *   int32 [n]): t. */
+int mh_tri_area64(mh_ctx *ctx, const double *vertices, int nv, const int32_t *faces, int nf, double *area, void *stream);
+int mh_mesh_sample(mh_ctx *ctx, const double *vertices, const double *normals, int nv, const int32_t *faces, int nf,
+                   const long long *bounds, const double *uniforms, int n, const double *bust_to_origin, float *out_points,
+                   float *out_normals, int32_t *out_triangle, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

@@ -1127,6 +1127,28 @@ extern "C" int mh_scalp_emit(mh_ctx *ctx, const float *pts, const long long *off
                     "mh_scalp_emit");
 }
 
+// ---- scalp sampling (HairGrow.py:880-897) ---------------------------------------------------------------------------
+extern "C" int mh_tri_area64(mh_ctx *ctx, const double *vertices, int nv, const int32_t *faces, int nf, double *area,
+                             void *stream) {
+    if (nf == 0) return MH_OK;
+    if (!ctx || !vertices || !faces || !area || nv < 1 || nf < 0) return fail(MH_ERR_ARG, "mh_tri_area64: bad arguments");
+    return launched(mh_launch_tri_area64(vertices, faces, nf, area, (hipStream_t)stream), "mh_tri_area64");
+}
+
+extern "C" int mh_mesh_sample(mh_ctx *ctx, const double *vertices, const double *normals, int nv, const int32_t *faces,
+                              int nf, const long long *bounds, const double *uniforms, int n, const double *bust_to_origin,
+                              float *out_points, float *out_normals, int32_t *out_triangle, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !vertices || !normals || !faces || !bounds || !uniforms || !bust_to_origin || !out_points || !out_normals ||
+        nv < 1 || nf < 1 || n < 0)
+        return fail(MH_ERR_ARG, "mh_mesh_sample: bad arguments");
+    // points_to_voxel's voxel_min is a float32 tensor that promotes against the float64 points; its voxel size is 0.005 / 2
+    const double vmin[3] = {(double)-0.32f, (double)-0.32f, (double)-0.24f};
+    return launched(mh_launch_mesh_sample(vertices, normals, faces, nf, (const int64_t *)bounds, uniforms, n, bust_to_origin,
+                                          vmin, 0.005 / 2, out_points, out_normals, out_triangle, (hipStream_t)stream),
+                    "mh_mesh_sample");
+}
+
 static int gabor_alloc(mh_ctx *ctx) {
     if (ctx->gabor) return MH_OK;
     MH_HIP(hipSetDevice(ctx->device));

@@ -223,4 +223,11 @@ int mh_launch_scalp_emit(const float *P, const int64_t *offs, int n, const uint8
                          const int32_t *best_idx, const int64_t *noffs, const float4 *vox, int W, int H, int Z,
                          double ratio_thr, float *Pn, uint8_t *flags, double *out_ratio, float *similar, int32_t *counters,
                          hipStream_t st);
+
+// ---- meshsample.hip (loads with its first launch)
+int mh_launch_tri_area64(const double *verts, const int32_t *faces, int nf, double *area, hipStream_t st);
+int mh_launch_mesh_sample(const double *verts, const double *normals, const int32_t *faces, int nf, const int64_t *bounds,
+                          const double *uniforms, int n, const double *bust /* host [3] */,
+                          const double *vmin /* host [3] */, double vs, float *out_pts, float *out_nrm, int32_t *out_tri,
+                          hipStream_t st);
 }

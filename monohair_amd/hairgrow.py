@@ -4,7 +4,8 @@ GenerateGuideStrandFromScalp :226-265, randomlyGenerateSegments :269-299, VoxelT
 consumer of Ori3D.mat / Occ3D.mat, and the segment connection that follows it
 (find_connect_info :434-590 with connect_segments :303-420, the connect_segments stage of __main__ :925-952), and the
 scalp attachment that ends the pipeline (connect_to_scalp :606-812, WorldToVoxel :826-835, the connect_scalp stage of
-__main__ :954-976, csrc/hairscalp.hip).
+__main__ :954-976, csrc/hairscalp.hip), and the scalp samples the whole stage starts from (__main__ :880-897,
+csrc/meshsample.hip).
 
 All seeds are traced in parallel by the HIP kernels of csrc/hairgrow.hip; the sequential `flag` gate only decides
 which finished traces are kept and is replayed afterwards (mh_strands_accept).  The jitter of every trace() call
@@ -17,7 +18,7 @@ import torch
 
 from . import _lib
 from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
-                         points_to_voxel, save_hair_strands, voxel_to_points)
+                         points_to_voxel, read_obj_normals, save_hair_strands, voxel_to_points)
 from .strand_smooth import smooth_strands
 
 _KNN_K = 50                                                      # k of the reference's end queries
@@ -453,14 +454,76 @@ class HairGrowing:
         return out
 
 
+def scalp_allocation(area, n):
+    """Open3D's stratified allocation of n samples to triangles of the given areas (float64 [nf]): the bounds B [nf] int64,
+    B[t] = floor(n * C[t] + 0.5) with C = cumsum(area / area.sum()) and B[nf-1] = n.  Sample i belongs to the first triangle
+    t with B[t] > i, so triangle t receives B[t] - B[t-1] samples, in triangle order, whatever the random stream; a
+    triangle of zero area receives none."""
+    area = np.asarray(area, dtype=np.float64).reshape(-1)
+    n = int(n)
+    if area.size == 0 or n < 0 or not np.isfinite(area).all() or (area < 0).any() or not area.sum() > 0:
+        raise _lib.MhError("scalp_allocation: needs n >= 0 and finite, non-negative areas with a positive sum")
+    C = np.cumsum(area / area.sum())
+    B = np.minimum(np.floor(n * C + 0.5), float(n)).astype(np.int64)      # (a C[t] that rounding took above 1 must not pass n)
+    B[-1] = n
+    return B
+
+
+def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, device="cuda:0", mesh=None, uniforms=None,
+                 return_details=False):
+    """The scalp samples of HairGrow.py's __main__ (:880-897): number_of_points points of the mesh at scalp_path with
+    interpolated vertex normals (Open3D's sample_points_uniformly, use_triangle_normal=False), shifted by bust_to_origin
+    and taken to voxel space -> (points_voxel, normals_voxel), float32 [n,3] tensors on `device`, exactly what tracing
+    receives.  The reference draws from an unseeded generator; here the uniforms are
+    np.random.default_rng(seed).random((n, 2)), so a seed repeats a run.  mesh: (vertices, faces, vertex normals) in place
+    of the file; uniforms: float64 [n,2] in [0,1) in place of the seeded draw.  The triangle areas and the samples are
+    computed by csrc/meshsample.hip; the allocation in between is scalp_allocation.  return_details: also return
+    dict(area [nf] float64, bounds [nf] int64, triangle [n] int32 tensor: the triangle of every sample)."""
+    if not torch.cuda.is_available():
+        raise _lib.MhError("sample_scalp needs a ROCm GPU (no CPU fallback)")
+    v, f, vn = read_obj_normals(scalp_path) if mesh is None else mesh
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3)
+    vn = np.ascontiguousarray(vn, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(f).reshape(-1, 3)
+    n, nv, nf = int(number_of_points), v.shape[0], f.shape[0]
+    if nv == 0 or nf == 0 or vn.shape[0] != nv or n < 0 or f.min() < 0 or f.max() >= nv:
+        raise _lib.MhError("sample_scalp: needs a mesh with faces, one normal per vertex and face indices inside it")
+    u = np.random.default_rng(seed).random((n, 2)) if uniforms is None else np.ascontiguousarray(uniforms, np.float64)
+    if u.shape != (n, 2) or not ((u >= 0) & (u < 1)).all():
+        raise _lib.MhError("sample_scalp: uniforms must be [n,2] in [0,1)")
+    bust = np.ascontiguousarray(np.asarray(bust_to_origin, dtype=np.float64).reshape(3))
+    dev, L = torch.device(device), _lib.lib()
+    ctx = _ctx_for(dev)
+    td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)    # noqa: E731
+    v_d, vn_d, f_d = td(v), td(vn), td(f.astype(np.int32))
+    area = torch.empty((nf,), dtype=torch.float64, device=dev)
+    pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    tri = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.mh_tri_area64(ctx, _lib.ptr(v_d), nv, _lib.ptr(f_d), nf, _lib.ptr(area), _lib.stream_ptr()),
+                   "mh_tri_area64")
+        area_h = area.cpu().numpy()
+        B = scalp_allocation(area_h, n)
+        B_d, u_d = td(B), td(u)
+        _lib.check(L.mh_mesh_sample(ctx, _lib.ptr(v_d), _lib.ptr(vn_d), nv, _lib.ptr(f_d), nf, _lib.ptr(B_d), _lib.ptr(u_d),
+                                    n, _hp(bust), _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(tri), _lib.stream_ptr()),
+                   "mh_mesh_sample")
+    if return_details:
+        return pts, nrm, dict(area=area_h, bounds=B, triangle=tri)
+    return pts, nrm
+
+
 def generate_segments(occ_path, ori_path, scalp_points_voxel, scalp_normals_voxel, save_path, bust_to_origin,
-                      grow_threshold=0.8, device="cuda:0", write_smooth=False, occ=None, ori=None):
+                      grow_threshold=0.8, device="cuda:0", write_smooth=False, occ=None, ori=None, solver=None):
     """The `generate_segments` stage of HairGrow.py's __main__ (:897-920): scalp_segment.hair + num_root.npy, and with
     write_smooth also the Laplacian-smoothed copy scalp_segment_smooth.hair (:914-917).  occ / ori: the readers' arrays
-    in place of the two files.  Returns the unsmoothed segments."""
+    in place of the two files; solver: a HairGrowing of that volume to use instead of building one.  Returns the unsmoothed
+    segments."""
     import os
 
-    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
+    if solver is None:
+        solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
     strands, num_root = solver.GenerateGuideStrandFromScalp(scalp_points_voxel, scalp_normals_voxel, None,
                                                             grow_threshold)
     world = solver.VoxelToWorld(strands, bust_to_origin)
@@ -473,11 +536,11 @@ def generate_segments(occ_path, ori_path, scalp_points_voxel, scalp_normals_voxe
 
 
 def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect_dot_threshold=0.7, occ_path=None,
-                     ori_path=None, device="cuda:0", occ=None, ori=None):
+                     ori_path=None, device="cuda:0", occ=None, ori=None, solver=None):
     """The `connect_segments` stage of HairGrow.py's __main__ (:925-952): reads scalp_segment.hair and num_root.npy
     from save_path, joins the non-root segments (shifted by bust_to_origin) with find_connect_info on the volume of
-    occ_path / ori_path (or the arrays occ / ori), smooths every strand (4.0, 2.0) and writes strands.hair.  Returns
-    (strands, solver)."""
+    occ_path / ori_path (or the arrays occ / ori, or the given solver), smooths every strand (4.0, 2.0) and writes
+    strands.hair.  Returns (strands, solver)."""
     import os
 
     segment, points = load_strand(os.path.join(save_path, "scalp_segment.hair"))
@@ -491,7 +554,8 @@ def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect
             strand += bust
         strands.append(strand)
         beg += seg
-    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
+    if solver is None:
+        solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
     connected = solver.find_connect_info(strands[num_root:], connect_threshold, connect_dot_threshold)
     new_strands = strands[:num_root] + [c - bust for c in connected]
     new_strands = smooth_strands(new_strands, 4.0, 2.0, device=device)
@@ -500,18 +564,19 @@ def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect
 
 
 def connect_scalp(save_path, bust_to_origin, out_ratio, occ_path=None, ori_path=None, device="cuda:0", occ=None, ori=None,
-                  infer_inner=False):
+                  infer_inner=False, solver=None):
     """The `connect_scalp` stage of HairGrow.py's __main__ (:954-976): reads strands.hair and num_root.npy from save_path,
     attaches the floating strands in voxel space (HairGrowing.connect_to_scalp on the volume of occ_path / ori_path or the
-    arrays occ / ori), returns to world units, smooths every strand (4.0, 2.0) and writes connected_strands.hair.
-    out_ratio: the case's HairGenerate.out_ratio.  Returns (strands, solver)."""
+    arrays occ / ori, or the given solver), returns to world units, smooths every strand (4.0, 2.0) and writes
+    connected_strands.hair.  out_ratio: the case's HairGenerate.out_ratio.  Returns (strands, solver)."""
     import os
 
     segment, points = load_strand(os.path.join(save_path, "strands.hair"))
     num_root = int(np.load(os.path.join(save_path, "num_root.npy")))
     bust = np.asarray(bust_to_origin, dtype=np.float64)
     strands = np.split(points, np.cumsum(segment)[:-1]) if len(segment) else []
-    solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
+    if solver is None:
+        solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
     connected = solver.connect_to_scalp(solver.WorldToVoxel(strands, bust), num_root, out_ratio, infer_inner)
     world = []
     for ss in connected:

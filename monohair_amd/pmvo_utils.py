@@ -173,6 +173,46 @@ def vertex_normals(vertices, faces):
     return n / np.maximum(ln, 1e-12)
 
 
+def read_obj_normals(path):
+    """(vertices [N,3] f64, faces [M,3] int, normals [N,3] f64) of an OBJ whose per-vertex normals are its own `vn` records,
+    reached through the `v/vt/vn` or `v//vn` indices of the faces (where a vertex is given several, the last face corner
+    wins) -- what Open3D's read_triangle_mesh hands HairGrow.py:880.  Polygons are fan-triangulated.  A vertex that no face
+    uses keeps a zero normal (nothing is ever sampled there).  A file without `vn`, or one with a face corner that names no
+    normal, gets vertex_normals(v, f) instead, whose direction follows the winding of the faces: Open3D returns a mesh
+    without vertex normals for such a file and the reference fails on it (its sampled cloud has no normals)."""
+    vs, vns, fs, fns = [], [], [], []
+    with open(path, "rb") as f:
+        for line in f:
+            if line.startswith(b"v "):
+                p = line.split()
+                vs.append([float(p[1]), float(p[2]), float(p[3])])
+            elif line.startswith(b"vn "):
+                p = line.split()
+                vns.append([float(p[1]), float(p[2]), float(p[3])])
+            elif line.startswith(b"f "):
+                vi, ni = [], []
+                for t in line.split()[1:]:
+                    parts = t.split(b"/")
+                    i = int(parts[0])
+                    vi.append(i - 1 if i > 0 else len(vs) + i)
+                    j = int(parts[2]) if len(parts) >= 3 and parts[2] else 0
+                    ni.append(-1 if j == 0 else (j - 1 if j > 0 else len(vns) + j))
+                for k in range(1, len(vi) - 1):
+                    fs.append([vi[0], vi[k], vi[k + 1]])
+                    fns.append([ni[0], ni[k], ni[k + 1]])
+    verts = np.asarray(vs, dtype=np.float64).reshape(-1, 3)
+    faces = np.asarray(fs, dtype=np.int64).reshape(-1, 3)
+    fn = np.asarray(fns, dtype=np.int64).reshape(-1)
+    if len(vns) and len(fn) and (fn >= 0).all():
+        vn = np.asarray(vns, dtype=np.float64).reshape(-1, 3)
+        if fn.max() >= len(vn) or faces.min() < 0 or faces.max() >= len(verts):
+            raise ValueError("read_obj_normals: %s: a face index is out of range" % path)
+        normals = np.zeros_like(verts)
+        normals[faces.reshape(-1)] = vn[fn]          # repeated indices: the last assignment stays
+        return verts, faces, normals
+    return verts, faces, vertex_normals(verts, faces)
+
+
 def load_bust(path):
     """(vertices, faces, normals) of the bust mesh (PMVO_utils.py:176-181)."""
     v, f = read_obj(path)

@@ -208,7 +208,7 @@ def write_case(root, case="synthetic_sphere", V=24, H=480, W=270, seed=0, scale=
     `python PMVO.py --yaml=configs/reconstruct/<case>` runs through the real loaders:
       ours/cam_params.json, capture_images/<view>.png, render_depth/<view>.npy [H,W,3] f32,
       best_ori/<view>.png (u8 degrees), conf/<view>.png (u8), hair_mask/<view>.png (BGR u8),
-      ours/colmap_points.obj (the sphere), ours/bust_long_tsfm.obj, ours/scalp_tsfm.obj."""
+      ours/colmap_points.obj (the sphere), ours/bust_long_tsfm.obj, ours/scalp_tsfm.obj (with `vn` records)."""
     import json
     import os
 
@@ -233,7 +233,9 @@ def write_case(root, case="synthetic_sphere", V=24, H=480, W=270, seed=0, scale=
         Image.fromarray(np.repeat(m8[..., None], 3, axis=2)).save(os.path.join(base, "hair_mask", name + ".png"))
         Image.fromarray(c8).save(os.path.join(base, "capture_images", name + ".png"))
 
-    def sphere_obj(path, radius, n_lat=48, n_lon=96, y_min=None):
+    def sphere_obj(path, radius, n_lat=48, n_lon=96, y_min=None, normals=False):
+        """normals: also write the outward unit normals as `vn` records, referenced by `v//vn` faces -- what a fitted
+        scalp_tsfm.obj carries and HairGrow.py reads (the vertex lines and the triangles stay the same)"""
         vs, fs = [], []
         for a in range(n_lat + 1):
             th = math.pi * a / n_lat
@@ -252,10 +254,16 @@ def write_case(root, case="synthetic_sphere", V=24, H=480, W=270, seed=0, scale=
         with open(path, "w") as f:
             for v in vs:
                 f.write("v %.9f %.9f %.9f\n" % v)
+            if normals:
+                for v in vs:
+                    f.write("vn %.9f %.9f %.9f\n" % tuple(c / radius for c in v))
             for t in fs:
-                f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
+                if normals:
+                    f.write("f %d//%d %d//%d %d//%d\n" % tuple(i + 1 for i in t for _ in range(2)))
+                else:
+                    f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
 
     sphere_obj(os.path.join(base, "ours", "colmap_points.obj"), SPHERE_R, n_lat=4 * res // 8, n_lon=8 * res // 8)
     sphere_obj(os.path.join(base, "ours", "bust_long_tsfm.obj"), 0.09, 24, 48)
-    sphere_obj(os.path.join(base, "ours", "scalp_tsfm.obj"), 0.10, 24, 48, y_min=0.03)
+    sphere_obj(os.path.join(base, "ours", "scalp_tsfm.obj"), 0.10, 24, 48, y_min=0.03, normals=True)
     return base
