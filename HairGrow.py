@@ -3,7 +3,8 @@
 (config_parser :837-873, __main__ :876-976):
 
     python HairGrow.py --yaml=configs/reconstruct/<case> [--PMVO.infer_inner] [--HairGenerate.generate_segments=]
-                       [--HairGenerate.connect_segments=] [--HairGenerate.connect_scalp=] [--a.b=v]
+                       [--HairGenerate.connect_segments=] [--HairGenerate.connect_scalp=] [--scalp_diffusion]
+                       [--HairGenerate.diffuse_scalp] [--a.b=v]
 
 in : data/<case>/output/<name>/{refine|full}/{Occ3D,Ori3D}.mat (PMVO.py), data/<case>/ours/scalp_tsfm.obj
 out: in the same directory scalp_samples.npz, scalp_segment.hair, scalp_segment_smooth.hair, num_root.npy, strands.hair,
@@ -15,6 +16,9 @@ HairGenerate.num_scalp_samples points with interpolated normals sampled from the
 reference samples them with an unseeded generator; here the draw follows `seed`, the samples are saved to
 scalp_samples.npz (`points`, `normals`: float32, voxel units, as tracing receives them), and
 --HairGenerate.scalp_samples=<file.npz> feeds such a file back in place of sampling.  One HairGrowing serves all stages.
+With --scalp_diffusion the stages read Occ3D_diffusion.mat / Ori3D_diffusion.mat, as in the reference, which has no
+command that writes them: here a stage in front (csrc/hairdiffuse.hip, the reference's library function diffusion_scalp
+on the scalp samples of the run) writes the two files when one is missing, or always with --HairGenerate.diffuse_scalp.
 All arithmetic runs in the HIP library; this file is host orchestration.
 """
 import json
@@ -30,6 +34,8 @@ from monohair_amd import options
 HAIRGENERATE_DEFAULTS = dict(connect_threshold=0.005, grow_threshold=0.8, connect_dot_threshold=0.7, generate_segments=True,
                              connect_segments=True, connect_scalp=True, out_ratio=0.5, num_scalp_samples=60000,
                              scalp_samples=None)
+# a key no case file carries, consulted only when `scalp_diffusion` is set: write the _diffusion.mat files even if they exist
+HAIRGENERATE_SWITCHES = dict(diffuse_scalp=False)
 
 
 def config_parser(argv=None):
@@ -37,7 +43,7 @@ def config_parser(argv=None):
     opt_cmd = options.parse_arguments(sys.argv[1:] if argv is None else argv)
     args = options.set(opt_cmd=opt_cmd)
     hg = args.setdefault("HairGenerate", options.Opt())
-    for key, value in HAIRGENERATE_DEFAULTS.items():
+    for key, value in list(HAIRGENERATE_DEFAULTS.items()) + list(HAIRGENERATE_SWITCHES.items()):
         hg.setdefault(key, value)
     args.output_path = os.path.join(args.data.root, args.data.case, args.output_root, args.name)
     os.makedirs(args.output_path, exist_ok=True)
@@ -83,7 +89,7 @@ def run(args, scalp_points=None, scalp_normals=None):
     read after the device has finished."""
     import torch
 
-    from monohair_amd.hairgrow import HairGrowing, connect_scalp, connect_segments, generate_segments
+    from monohair_amd.hairgrow import HairGrowing, connect_scalp, connect_segments, diffuse_scalp, generate_segments
 
     hg, dev = args.HairGenerate, args.device
     T = {}
@@ -97,6 +103,12 @@ def run(args, scalp_points=None, scalp_normals=None):
 
     t_all = time.perf_counter()
     os.makedirs(args.save_path, exist_ok=True)
+    if args.get("scalp_diffusion") and (hg.diffuse_scalp or not (os.path.exists(args.data.Occ3D_path) and
+                                                                 os.path.exists(args.data.Ori3D_path))):
+        # the reference has the switch but no command that writes the two files it then reads
+        if scalp_points is None or scalp_normals is None:
+            scalp_points, scalp_normals = timed("scalp_samples_s", lambda: scalp_samples(args))
+        timed("diffuse_scalp_s", lambda: diffuse_scalp(args.save_path, scalp_points, scalp_normals, device=dev))
     solver = timed("load_volume_s", lambda: HairGrowing(args.data.Occ3D_path, args.data.Ori3D_path, device=dev,
                                                         image_size=args.data.image_size))
     if hg.generate_segments:

@@ -453,6 +453,32 @@ int mh_mesh_sample(mh_ctx *ctx, const double *vertices, const double *normals, i
                    const long long *bounds, const double *uniforms, int n, const double *bust_to_origin, float *out_points,
                    float *out_normals, int32_t *out_triangle, void *stream);
 
+/* Scalp diffusion (the reference's diffusion_scalp, Utils/PMVO_utils.py:467-593): the volumes HairGrow.py reads when
+ * `scalp_diffusion` is set.  occ [Z,H,W] and ori [3][Z,H,W] (planar) are the float32 volumes as the .mat files hold them
+ * (no y/z flip); points / normals [n,3] are float32 world-space scalp samples.  voxel_min and the voxel size are the
+ * reference's constants (-0.32, -0.32, -0.24 as float32; 0.005 / 2).
+ * mh_diffuse_walk: per sample the walk along its normal (:494-536) -> status (0 accepted, 1 the sample lies in hair, 2 ten
+ *   steps without an end, 3 nine restarts without an end, 4 the walk left the volume -- the reference's indexing raises or
+ *   wraps there), steps, end_points [n,3] (point_set[-1]), first_normals / last_normals [n,3] (normal_set[0] / [-1]).
+ * mh_diffuse_arc: row_offsets [n+1] (int64) = exclusive scan of steps + 1 over the accepted samples, rows = its last entry.
+ *   Per row the float64 Hermite sample (:545-547, scipy's power-form evaluation), its forward-difference tangent (:548), the
+ *   unit tangent (:560), the voxel (x, y, z) of the sample (:561; -1 where it leaves the volume) and the sort key (the
+ *   linear voxel z*H*W + y*W + x, or W*H*Z for a row outside).
+ * mh_diffuse_splat: the rows grouped by voxel with a STABLE sort (mh_sort_keys on the keys -> order; mh_segment_heads on the
+ *   sorted keys -> seg_start, head_keys, meta).  Per touched voxel the unit tangents are added in row order into a float32
+ *   accumulator through a float64 sum (:563-567) and combined in place: ori += (1 - occ) * acc / max(count, 1e-6), occ +=
+ *   (1 - occ) (:568-592).  Untouched voxels are not written. */
+int mh_diffuse_walk(mh_ctx *ctx, const float *occ, const float *ori, int W, int H, int Z, const float *points,
+                    const float *normals, int n, int32_t *status, int32_t *steps, float *end_points, float *first_normals,
+                    float *last_normals, void *stream);
+int mh_diffuse_arc(mh_ctx *ctx, const float *points, const float *end_points, const float *first_normals,
+                   const float *last_normals, const int32_t *steps, const long long *row_offsets, int n, int rows, int W,
+                   int H, int Z, double *sample, double *tangent, double *unit, int32_t *voxel, unsigned long long *keys,
+                   void *stream);
+int mh_diffuse_splat(mh_ctx *ctx, const int32_t *seg_start, const unsigned long long *head_keys, const int32_t *meta,
+                     const int32_t *order, const double *unit, int rows, int W, int H, int Z, float *occ, float *ori,
+                     void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

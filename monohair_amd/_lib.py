@@ -70,6 +70,9 @@ _SIGS = {
     "mh_scalp_emit": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.c_double, vp, vp, vp, vp, vp, vp]),
     "mh_tri_area64": (ci, [vp, vp, ci, vp, ci, vp, vp]),
     "mh_mesh_sample": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "mh_diffuse_walk": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "mh_diffuse_arc": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "mh_diffuse_splat": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

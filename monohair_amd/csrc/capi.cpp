@@ -1149,6 +1149,49 @@ extern "C" int mh_mesh_sample(mh_ctx *ctx, const double *vertices, const double 
                     "mh_mesh_sample");
 }
 
+// ---- scalp diffusion (Utils/PMVO_utils.py:467-593) ------------------------------------------------------------------
+static bool diffuse_dims_ok(int W, int H, int Z) {
+    return W >= 1 && H >= 1 && Z >= 1 && (long long)W * H * Z < (1ll << 31);
+}
+
+extern "C" int mh_diffuse_walk(mh_ctx *ctx, const float *occ, const float *ori, int W, int H, int Z, const float *points,
+                               const float *normals, int n, int32_t *status, int32_t *steps, float *end_points,
+                               float *first_normals, float *last_normals, void *stream) {
+    if (n == 0) return MH_OK;
+    if (!ctx || !occ || !ori || !points || !normals || !status || !steps || !end_points || !first_normals ||
+        !last_normals || n < 0 || !diffuse_dims_ok(W, H, Z))
+        return fail(MH_ERR_ARG, "mh_diffuse_walk: bad arguments");
+    return launched(mh_launch_diffuse_walk(occ, ori, W, H, Z, points, normals, n, status, steps, end_points, first_normals,
+                                           last_normals, (hipStream_t)stream),
+                    "mh_diffuse_walk");
+}
+
+extern "C" int mh_diffuse_arc(mh_ctx *ctx, const float *points, const float *end_points, const float *first_normals,
+                              const float *last_normals, const int32_t *steps, const long long *row_offsets, int n, int rows,
+                              int W, int H, int Z, double *sample, double *tangent, double *unit, int32_t *voxel,
+                              unsigned long long *keys, void *stream) {
+    if (rows == 0) return MH_OK;
+    if (!ctx || !points || !end_points || !first_normals || !last_normals || !steps || !row_offsets || !sample ||
+        !tangent || !unit || !voxel || !keys || n < 1 || rows < 0 || !diffuse_dims_ok(W, H, Z))
+        return fail(MH_ERR_ARG, "mh_diffuse_arc: bad arguments");
+    return launched(mh_launch_diffuse_arc(points, end_points, first_normals, last_normals, steps,
+                                          (const int64_t *)row_offsets, n, rows, W, H, Z, sample, tangent, unit, voxel, keys,
+                                          (hipStream_t)stream),
+                    "mh_diffuse_arc");
+}
+
+extern "C" int mh_diffuse_splat(mh_ctx *ctx, const int32_t *seg_start, const unsigned long long *head_keys,
+                                const int32_t *meta, const int32_t *order, const double *unit, int rows, int W, int H, int Z,
+                                float *occ, float *ori, void *stream) {
+    if (rows == 0) return MH_OK;
+    if (!ctx || !seg_start || !head_keys || !meta || !order || !unit || !occ || !ori || rows < 0 ||
+        !diffuse_dims_ok(W, H, Z))
+        return fail(MH_ERR_ARG, "mh_diffuse_splat: bad arguments");
+    return launched(mh_launch_diffuse_splat(seg_start, head_keys, meta, order, unit, rows, W, H, Z, occ, ori,
+                                            (hipStream_t)stream),
+                    "mh_diffuse_splat");
+}
+
 static int gabor_alloc(mh_ctx *ctx) {
     if (ctx->gabor) return MH_OK;
     MH_HIP(hipSetDevice(ctx->device));

@@ -230,4 +230,15 @@ int mh_launch_mesh_sample(const double *verts, const double *normals, const int3
                           const double *uniforms, int n, const double *bust /* host [3] */,
                           const double *vmin /* host [3] */, double vs, float *out_pts, float *out_nrm, int32_t *out_tri,
                           hipStream_t st);
+
+// ---- hairdiffuse.hip (loads with its first launch)
+int mh_launch_diffuse_walk(const float *occ, const float *ori, int W, int H, int Z, const float *pts, const float *nrm,
+                           int n, int32_t *status, int32_t *steps, float *end_pt, float *first_n, float *last_n,
+                           hipStream_t st);
+int mh_launch_diffuse_arc(const float *pts, const float *end_pt, const float *first_n, const float *last_n,
+                          const int32_t *steps, const int64_t *offs, int n, int rows, int W, int H, int Z, double *sample,
+                          double *tangent, double *unit, int32_t *voxel, unsigned long long *keys, hipStream_t st);
+int mh_launch_diffuse_splat(const int32_t *seg_start, const unsigned long long *head_keys, const int32_t *meta,
+                            const int32_t *order, const double *unit, int rows, int W, int H, int Z, float *occ, float *ori,
+                            hipStream_t st);
 }

@@ -5,7 +5,8 @@ consumer of Ori3D.mat / Occ3D.mat, and the segment conne
 (find_connect_info :434-590 with connect_segments :303-420, the connect_segments stage of __main__ :925-952), and the
 scalp attachment that ends the pipeline (connect_to_scalp :606-812, WorldToVoxel :826-835, the connect_scalp stage of
 __main__ :954-976, csrc/hairscalp.hip), and the scalp samples the whole stage starts from (__main__ :880-897,
-csrc/meshsample.hip).
+csrc/meshsample.hip), and the scalp-diffused volumes the stage reads when `scalp_diffusion` is set (diffusion_scalp of
+Utils/PMVO_utils.py:467-593, csrc/hairdiffuse.hip).
 
 All seeds are traced in parallel by the HIP kernels of csrc/hairgrow.hip; the sequential `flag` gate only decides
 which finished traces are kept and is replayed afterwards (mh_strands_accept).  The jitter of every trace() call
@@ -18,7 +19,7 @@ import torch
 
 from . import _lib
 from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
-                         points_to_voxel, read_obj_normals, save_hair_strands, voxel_to_points)
+                         points_to_voxel, read_obj_normals, save_hair_strands, save_volume_mat_sparse, voxel_to_points)
 from .strand_smooth import smooth_strands
 
 _KNN_K = 50                                                      # k of the reference's end queries
@@ -512,6 +513,103 @@ def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, dev
     if return_details:
         return pts, nrm, dict(area=area_h, bounds=B, triangle=tri)
     return pts, nrm
+
+
+DIFFUSE_STATUS = ("accepted", "inside hair", "ten steps", "nine restarts", "left the volume")
+
+
+def diffusion_scalp(points, normals, ori, occ, device="cuda:0", return_details=False):
+    """The reference's diffusion_scalp (Utils/PMVO_utils.py:467-593): from every scalp sample a walk along its normal in
+    steps of one voxel until it meets hair whose orientation agrees (else the normal is bent towards the orientation found
+    and the walk restarts), a cubic Hermite arc from the sample to that voxel, and the arcs' unit tangents averaged into the
+    empty voxels they cross.  points / normals [n,3]: world-space samples; ori [3,Z,Y,X], occ [1,Z,Y,X]: the volume in the
+    .mat convention (not HairGrowing's flipped copy).  Returns (ori, occ), new float32 tensors of the same shapes on
+    `device`.  Everything is computed by csrc/hairdiffuse.hip in the reference's order of operations (float32 walk, float64
+    arc, rows added per voxel in row order), bit for bit; there is no CPU fallback.
+
+    return_details: also a dict with status [n] (index into DIFFUSE_STATUS) and step [n] per sample, end_point /
+    first_normal / last_normal [n,3], total_sample and total_normal [R,3] float64 (what the reference saves as
+    total_sample.npy / total_normal.npy), total_normal_unit [R,3] and voxel [R,3] (x, y, z; int64) per row, and
+    left_volume: the number of samples abandoned because their walk left the volume.
+
+    Deliberate differences: a walk whose voxel index leaves [0, dim) is abandoned with its own status and counted (the
+    reference raises IndexError there, or wraps around for small negative indices), and a row of an arc outside the volume
+    is left out; with no accepted sample the volumes come back unchanged (the reference fails at np.concatenate([])); the
+    two .npy files are not written, their contents are in the details."""
+    if not torch.cuda.is_available():
+        raise _lib.MhError("diffusion_scalp needs a ROCm GPU (no CPU fallback)")
+    dev, L = torch.device(device), _lib.lib()
+    ctx = _ctx_for(dev)
+    pts = torch.as_tensor(points).to(dev).type(torch.float).reshape(-1, 3).contiguous()
+    nrm = torch.as_tensor(normals).to(dev).type(torch.float).reshape(-1, 3).contiguous()
+    ori_o = torch.as_tensor(ori).to(dev).type(torch.float).contiguous().clone()
+    occ_o = torch.as_tensor(occ).to(dev).type(torch.float).contiguous().clone()
+    if occ_o.dim() != 4 or occ_o.shape[0] != 1 or ori_o.shape != (3,) + tuple(occ_o.shape[1:]) or nrm.shape != pts.shape:
+        raise _lib.MhError("diffusion_scalp: needs points and normals [n,3], ori [3,Z,Y,X] and occ [1,Z,Y,X]")
+    Z, H, W = (int(v) for v in occ_o.shape[1:])
+    n = pts.shape[0]
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    step = torch.empty((n,), dtype=torch.int32, device=dev)
+    end, first, last = (torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    R = 0
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr()
+        _lib.check(L.mh_diffuse_walk(ctx, _lib.ptr(occ_o), _lib.ptr(ori_o), W, H, Z, _lib.ptr(pts), _lib.ptr(nrm), n,
+                                     _lib.ptr(status), _lib.ptr(step), _lib.ptr(end), _lib.ptr(first), _lib.ptr(last), st),
+                   "mh_diffuse_walk")
+        offs = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        if n:
+            torch.cumsum(torch.where(status == 0, step.long() + 1, torch.zeros_like(step).long()), 0, out=offs[1:])
+            R = int(offs[-1])
+        assert R < 2 ** 31
+        sample, tangent, unit = (torch.empty((R, 3), dtype=torch.float64, device=dev) for _ in range(3))
+        voxel = torch.empty((R, 3), dtype=torch.int32, device=dev)
+        if R:
+            keys = torch.empty((R,), dtype=torch.int64, device=dev)
+            _lib.check(L.mh_diffuse_arc(ctx, _lib.ptr(pts), _lib.ptr(end), _lib.ptr(first), _lib.ptr(last), _lib.ptr(step),
+                                        _lib.ptr(offs), n, R, W, H, Z, _lib.ptr(sample), _lib.ptr(tangent), _lib.ptr(unit),
+                                        _lib.ptr(voxel), _lib.ptr(keys), st), "mh_diffuse_arc")
+            # rows grouped by voxel, in row order within a voxel: the sort is stable
+            scratch = torch.empty(int(L.mh_sort_scratch_bytes(R)), dtype=torch.uint8, device=dev)
+            skeys = torch.empty_like(keys)
+            order = torch.empty((R,), dtype=torch.int32, device=dev)
+            _lib.check(L.mh_sort_keys(ctx, _lib.ptr(keys), R, max(1, (W * H * Z).bit_length()), _lib.ptr(scratch),
+                                      scratch.numel(), _lib.ptr(skeys), _lib.ptr(order), st), "mh_sort_keys")
+            sel = torch.empty(int(L.mh_select_scratch_bytes(R)), dtype=torch.uint8, device=dev)
+            seg = torch.empty((R + 1,), dtype=torch.int32, device=dev)
+            heads = torch.empty((R,), dtype=torch.int64, device=dev)
+            meta = torch.empty((2,), dtype=torch.int32, device=dev)
+            _lib.check(L.mh_segment_heads(ctx, _lib.ptr(skeys), R, _lib.ptr(seg), _lib.ptr(heads), _lib.ptr(meta),
+                                          _lib.ptr(sel), sel.numel(), st), "mh_segment_heads")
+            _lib.check(L.mh_diffuse_splat(ctx, _lib.ptr(seg), _lib.ptr(heads), _lib.ptr(meta), _lib.ptr(order),
+                                          _lib.ptr(unit), R, W, H, Z, _lib.ptr(occ_o), _lib.ptr(ori_o), st),
+                       "mh_diffuse_splat")
+    if not return_details:
+        return ori_o, occ_o
+    return ori_o, occ_o, dict(status=status, step=step, end_point=end, first_normal=first, last_normal=last,
+                              total_sample=sample, total_normal=tangent, total_normal_unit=unit, voxel=voxel.long(),
+                              left_volume=int((status == 4).sum()))
+
+
+def diffuse_scalp(save_path, scalp_points_voxel, scalp_normals_voxel, device="cuda:0", occ_path=None, ori_path=None,
+                  return_details=False):
+    """The stage that writes the volumes HairGrow.py reads when `scalp_diffusion` is set: Occ3D.mat / Ori3D.mat of
+    save_path (or occ_path / ori_path) go through diffusion_scalp with the scalp samples of the run -- scalp_samples.npz's
+    float32 voxel-space points taken back to world units by voxel_to_points, the normals un-flipped (y and z negated
+    again) -- and come out as Occ3D_diffusion.mat / Ori3D_diffusion.mat in the same directory, in PMVO.py's layout and
+    dtype: get_ground_truth_3D_occ / _ori read back exactly the returned arrays.  Returns (ori [3,Z,Y,X], occ [1,Z,Y,X])."""
+    import os
+
+    occ = get_ground_truth_3D_occ(occ_path or os.path.join(save_path, "Occ3D.mat"))          # [Z,Y,X,1]
+    ori = get_ground_truth_3D_ori(ori_path or os.path.join(save_path, "Ori3D.mat"))          # [Z,Y,X,3]
+    pts = voxel_to_points(torch.as_tensor(scalp_points_voxel).cpu().type(torch.float).clone())
+    nrm = torch.as_tensor(scalp_normals_voxel).cpu().type(torch.float).clone()
+    nrm[..., 1:] *= -1
+    res = diffusion_scalp(pts, nrm, torch.from_numpy(ori).permute(3, 0, 1, 2), torch.from_numpy(occ).permute(3, 0, 1, 2),
+                          device=device, return_details=return_details)
+    save_volume_mat_sparse(os.path.join(save_path, "Occ3D_diffusion.mat"), os.path.join(save_path, "Ori3D_diffusion.mat"),
+                           res[1][0].cpu().numpy(), res[0].permute(1, 2, 3, 0).cpu().numpy())
+    return res
 
 
 def generate_segments(occ_path, ori_path, scalp_points_voxel, scalp_normals_voxel, save_path, bust_to_origin,

@@ -707,6 +707,31 @@ def save_ori_occ_mat_sparse(path, grid_resolution, voxels, ori, threads=1):
         list(pool.map(lambda j: write(*j), jobs))
 
 
+def save_volume_mat_sparse(occ_file, ori_file, occ, ori, threads=1):
+    """A dense float32 volume written as the two MAT-v5 files of save_ori_occ_mat (PMVO.py:753-764: Occ [Y,X,Z], Ori
+    [Y,X,3Z] with last index c*Z+z, float64) under the given file names, from its non-zero elements only.  occ [Z,Y,X],
+    ori [Z,Y,X,3] as the readers return them: get_ground_truth_3D_occ / _ori read back exactly these arrays."""
+    import ctypes
+
+    occ = np.asarray(occ, dtype=np.float32)
+    ori = np.asarray(ori, dtype=np.float32)
+    Z, Y, X = occ.shape
+    assert ori.shape == (Z, Y, X, 3)
+    L = _lib.lib()
+
+    def write(fname, name, dims, idx, val):
+        prefix, ndata = _mat5_prefix(name, dims)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        _lib.check(L.mh_mat_write_sparse(fname.encode(), prefix, len(prefix), ndata, idx.ctypes.data_as(ctypes.c_void_p),
+                                         val.ctypes.data_as(ctypes.c_void_p), len(idx), threads), "mh_mat_write_sparse")
+
+    z, y, x = np.nonzero(occ)
+    write(occ_file, "Occ", (Y, X, Z), y + Y * (x + X * z), occ[z, y, x])
+    z, y, x, c = np.nonzero(ori)
+    write(ori_file, "Ori", (Y, X, 3 * Z), y + Y * (x + X * (c * Z + z)), ori[z, y, x, c])
+
+
 class SparseMatWriter:
     """Ori3D.mat / Occ3D.mat of save_ori_occ_mat_sparse written in two phases: the constructor creates and maps both files
     and -- on a background thread per file -- makes the pages resident that the voxels of `candidate_points` fall on (every
