@@ -274,29 +274,17 @@ __global__ __launch_bounds__(256) void mh_occ_check_kernel(const double *__restr
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int64_t o = offs[i], n = offs[i + 1] - o;
-    bool box = false, bad = false;
+    int seen = n == 0 ? MH_VOX_REFUSED : 0;   // MH_VOX_BOX | MH_VOX_REFUSED over the strand's points
+    float sum = 0.0f;                          // in point order; read only when every point is inside
     for (int64_t k = 0; k < n; ++k) {
         const double *p = S + 3 * (o + k);
-        const int64_t x = (int64_t)rint((p[0] - vx) / vs), y = (int64_t)rint((-p[1] - vy) / vs),
-                      z = (int64_t)rint((-p[2] - vz) / vs);
-        box |= z >= 192 || y >= 256 || x >= 256;
-        bad |= x < -W || x >= W || y < -H || y >= H || z < -Z || z >= Z;
+        int64_t at;
+        const int r = mh_voxel_index((int64_t)rint((p[0] - vx) / vs), (int64_t)rint((-p[1] - vy) / vs),
+                                     (int64_t)rint((-p[2] - vz) / vs), W, H, Z, at);
+        seen |= r;
+        if (!r) sum += occ[at * ostride];
     }
-    if (box || bad || n == 0) {
-        status[i] = box ? 2 : 3;
-        return;
-    }
-    float sum = 0.0f;
-    for (int64_t k = 0; k < n; ++k) {
-        const double *p = S + 3 * (o + k);
-        int64_t x = (int64_t)rint((p[0] - vx) / vs), y = (int64_t)rint((-p[1] - vy) / vs),
-                z = (int64_t)rint((-p[2] - vz) / vs);
-        x += x < 0 ? W : 0;
-        y += y < 0 ? H : 0;
-        z += z < 0 ? Z : 0;
-        sum += occ[((z * H + y) * W + x) * ostride];
-    }
-    status[i] = (sum / (float)n > 0.8f) ? 1 : 0;
+    status[i] = (seen & MH_VOX_BOX) ? 2 : (seen ? 3 : ((sum / (float)n > 0.8f) ? 1 : 0));
 }
 
 // ---------------------------------------------------------------------------------------------- smoothing

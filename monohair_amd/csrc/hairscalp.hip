@@ -25,10 +25,6 @@ struct MhScalpGrid {   // uniform grid over the core points (mh_grid_build): cel
     int dx, dy, dz;
 };
 
-__device__ __forceinline__ int mh_sc_cell(float p, float o, float h, int d) {   // mh_cell_key_kernel's formula
-    return min(max((int)floorf((p - o) / h), 0), d - 1);
-}
-
 __device__ __forceinline__ unsigned long long mh_sc_min_u64(unsigned long long v) {
     for (int s = 1; s < MH_WAVE; s <<= 1) {
         const unsigned long long o = __shfl_xor(v, s);
@@ -47,8 +43,8 @@ __device__ __forceinline__ double mh_sc_sum_f64(double v) {
 template <class F>
 __device__ __forceinline__ void mh_sc_ball_scan(const float *__restrict__ core, MhScalpGrid g, float qx, float qy,
                                                 float qz, double r2, int lane, F fn) {
-    const int cx = mh_sc_cell(qx, g.ox, g.h, g.dx), cy = mh_sc_cell(qy, g.oy, g.h, g.dy),
-              cz = mh_sc_cell(qz, g.oz, g.h, g.dz);
+    const int cx = mh_grid_cell(qx, g.ox, g.h, g.dx), cy = mh_grid_cell(qy, g.oy, g.h, g.dy),
+              cz = mh_grid_cell(qz, g.oz, g.h, g.dz);
     const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dx - 1);
     for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dz - 1); ++z)
         for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dy - 1); ++y) {
@@ -290,20 +286,15 @@ __global__ __launch_bounds__(256) void mh_scalp_emit_kernel(
         seed[ax] = s0[ax] * 0.95f + N[3 * m + ax] * 0.05f;
         O[3 * m + ax] = seed[ax];
     }
-    bool box = false, bad = false;
+    int seen = 0;   // MH_VOX_BOX | MH_VOX_REFUSED over the points visited
     float occ_sum = 0.0f;
     double cos_sum = 0.0;
     auto visit = [&](const float *p, float o0, float o1, float o2) {   // one point of ss with its strand_ori
-        int64_t x = (int64_t)rintf(p[0]), y = (int64_t)rintf(p[1]), z = (int64_t)rintf(p[2]);   // torch.round: half to even
-        box |= z >= 192 || y >= 256 || x >= 256;   // the reference's three clauses reduce to these
-        if (x < -W || x >= W || y < -H || y >= H || z < -Z || z >= Z) {
-            bad = true;
-            return;
-        }
-        x += x < 0 ? W : 0;
-        y += y < 0 ? H : 0;
-        z += z < 0 ? Z : 0;
-        const float4 v = vox[((size_t)z * H + y) * W + x];   // {ori (y/z negated), occ}
+        int64_t at;   // torch.round: half to even
+        const int r = mh_voxel_index((int64_t)rintf(p[0]), (int64_t)rintf(p[1]), (int64_t)rintf(p[2]), W, H, Z, at);
+        seen |= r;
+        if (r & MH_VOX_REFUSED) return;
+        const float4 v = vox[at];   // {ori (y/z negated), occ}
         occ_sum += v.w;
         // torch.cosine_similarity: x / max(|x|, 1e-8) . y / max(|y|, 1e-8); max(cos, -cos) = |cos|
         const float na = fmaxf(sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z), 1e-8f),
@@ -324,9 +315,9 @@ __global__ __launch_bounds__(256) void mh_scalp_emit_kernel(
     }
     int st;      // 1 rooted, 2 out, 3 an index torch refuses
     float orat = 0.0f, sim = 0.0f;
-    if (box) {
+    if (seen & MH_VOX_BOX) {
         st = 2;   // leaves the 256 x 256 x 192 box: check False, out_ratio 0
-    } else if (bad) {
+    } else if (seen & MH_VOX_REFUSED) {
         st = 3;
     } else {
         const float ratio = occ_sum / (float)(m + 1);

@@ -56,19 +56,18 @@ __global__ __launch_bounds__(128) void mh_knn_kernel(MhGrid g, const float *__re
         const float *__restrict__ q = reinterpret_cast<const float *>(queries);
         dqx = (double)q[3 * qi], dqy = (double)q[3 * qi + 1], dqz = (double)q[3 * qi + 2];
     }
-    // the cell of the query: a float32 query by the formula of the data points' cells (mh_cell_key_kernel), a float64
-    // one from its exact coordinates -- rounding it to float32 first moves it by up to half an ulp of its magnitude, which
-    // is more than the reach margin below once the cells are small against the coordinates (1 km / 0.1 mm cells).  The
-    // clamp to the grid happens in floating point, so a query far outside never converts an out-of-range value to int.
+    // the cell of the query: a float32 query by the formula of the data points' cells (mh_grid_cell), a float64 one by the
+    // same steps on its exact coordinates -- rounding it to float32 first moves it by up to half an ulp of its magnitude,
+    // which is more than the reach margin below once the cells are small against the coordinates (1 km / 0.1 mm cells).
     int cx, cy, cz;
     if (q64) {
         cx = (int)fmin(fmax(floor((dqx - (double)g.ox) / (double)g.h), 0.0), (double)(g.dx - 1));
         cy = (int)fmin(fmax(floor((dqy - (double)g.oy) / (double)g.h), 0.0), (double)(g.dy - 1));
         cz = (int)fmin(fmax(floor((dqz - (double)g.oz) / (double)g.h), 0.0), (double)(g.dz - 1));
     } else {
-        cx = (int)fminf(fmaxf(floorf(((float)dqx - g.ox) / g.h), 0.0f), (float)(g.dx - 1));
-        cy = (int)fminf(fmaxf(floorf(((float)dqy - g.oy) / g.h), 0.0f), (float)(g.dy - 1));
-        cz = (int)fminf(fmaxf(floorf(((float)dqz - g.oz) / g.h), 0.0f), (float)(g.dz - 1));
+        cx = mh_grid_cell((float)dqx, g.ox, g.h, g.dx);
+        cy = mh_grid_cell((float)dqy, g.oy, g.h, g.dy);
+        cz = mh_grid_cell((float)dqz, g.oz, g.h, g.dz);
     }
     int st = 1;   // 1: ring limit reached (cells too small for this query), 2: candidate buffer overflow (too large)
     for (int ring = max(ring0, 1); ring <= MH_KNN_MAXRING; ++ring) {

@@ -327,6 +327,31 @@ __device__ __forceinline__ float mh_clampf(float x, float lo, float hi) {
     return x < lo ? lo : (x > hi ? hi : x);
 }
 
+// The cell of a coordinate on a uniform grid of `dim` cells of size h from `origin`, in float32.  A grid is correct only
+// while its data points (mh_cell_key_kernel), the k-NN's float32 queries (knn.hip) and the scalp balls (hairscalp.hip)
+// agree on this formula, so all three call it.  The clamp happens in floating point: a coordinate far outside the grid
+// never converts an out-of-range value to int, and NaN lands in cell 0.
+__device__ __forceinline__ int mh_grid_cell(float p, float origin, float h, int dim) {
+    return (int)fminf(fmaxf(floorf((p - origin) / h), 0.0f), (float)(dim - 1));
+}
+
+// The voxel that an already rounded index (x, y, z) reads in a [Z,H,W] volume, by the rules of the reference's occupancy
+// tests (HairGrow.py:517-528; random_move_strands, Utils/PMVO_utils.py:618-658).  The rounding stays with the caller.
+// -> MH_VOX_BOX when the index leaves the reference's hard-coded 256 x 256 x 192 box (its three clauses reduce to these; the
+// test then answers False), MH_VOX_REFUSED when it lies outside [-dim, dim), where torch's indexing raises IndexError; both
+// can be set.  lin: the linear index, a negative index wrapped as torch wraps it; written unless refused.
+#define MH_VOX_BOX 1
+#define MH_VOX_REFUSED 2
+__device__ __forceinline__ int mh_voxel_index(int64_t x, int64_t y, int64_t z, int W, int H, int Z, int64_t &lin) {
+    const int box = (z >= 192 || y >= 256 || x >= 256) ? MH_VOX_BOX : 0;
+    if (x < -W || x >= W || y < -H || y >= H || z < -Z || z >= Z) return box | MH_VOX_REFUSED;
+    x += x < 0 ? W : 0;
+    y += y < 0 ? H : 0;
+    z += z < 0 ? Z : 0;
+    lin = (z * H + y) * W + x;
+    return box;
+}
+
 // PMVO.compute_visible (PMVO.py:525-529)
 __device__ __forceinline__ float mh_soft_visible(float depth, float z255) {
     float d = z255 - depth;

@@ -15,10 +15,8 @@ __global__ __launch_bounds__(256) void mh_cell_key_kernel(const float *__restric
                                                           int32_t *__restrict__ vals) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
-    // the cell of a point, exactly as mh_knn_kernel computes the cell of a query
-    const int cx = min(max((int)floorf((pts[3 * i] - ox) / h), 0), dx - 1);
-    const int cy = min(max((int)floorf((pts[3 * i + 1] - oy) / h), 0), dy - 1);
-    const int cz = min(max((int)floorf((pts[3 * i + 2] - oz) / h), 0), dz - 1);
+    const int cx = mh_grid_cell(pts[3 * i], ox, h, dx), cy = mh_grid_cell(pts[3 * i + 1], oy, h, dy),
+              cz = mh_grid_cell(pts[3 * i + 2], oz, h, dz);
     keys[i] = (unsigned)((cz * dy + cy) * dx + cx);
     vals[i] = i;
 }

@@ -13,6 +13,8 @@ which finished traces are kept and is replayed afterwards (mh_strands_accept).  
 comes from torch's CPU generator in the order the reference draws it, so a seeded run reproduces the reference's
 CPU path bit for bit."""
 import ctypes
+import os
+import types
 
 import numpy as np
 import torch
@@ -20,28 +22,31 @@ import torch
 from . import _lib
 from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
                          points_to_voxel, read_obj_normals, save_hair_strands, save_volume_mat_sparse, voxel_to_points)
-from .strand_smooth import smooth_strands
+from .strand_smooth import pack_strands, smooth_strands, split_strands, strand_offsets
 
 _KNN_K = 50                                                      # k of the reference's end queries
 _VMIN64 = np.array([-0.32, -0.32, -0.24], np.float32).astype(np.float64)   # points_to_voxel's float32 voxel_min
 _TYPES = ("root", "tip")
+_OUTSIDE = "%s indexes outside the occupancy volume (the reference's torch indexing raises IndexError here)"
 
 
 def _hp(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _end_cells(ends, bound):
-    """Uniform grid over the strand ends with cells no smaller than `bound` (so every end closer than the bound lies in
-    one of the 27 cells around a query's), coarsened while it would have more than max(4n, 2^20) cells."""
-    lo = ends.min(0)
-    h = bound * 1.0001
-    cap = max(4 * ends.shape[0], 1 << 20)
+def _td(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def grid_dims(extent, radius, slack, n):
+    """(h, dims) of a uniform grid over n points spanning `extent` (float64 [3], from the grid's origin): cells of radius *
+    slack, so that everything within the radius of a point lies in the 27 cells around its own, doubled while there would
+    be more than max(4n, 2^20) of them."""
+    h = radius * slack
     while True:
-        cell = np.floor((ends - lo) / h).astype(np.int64)
-        dims = cell.max(0) + 1
-        if int(np.prod(dims)) <= cap:
-            return cell.astype(np.int32), [int(d) for d in dims]
+        dims = np.floor(extent / h).astype(np.int64) + 1
+        if int(np.prod(dims)) <= max(4 * n, 1 << 20):
+            return h, [int(d) for d in dims]
         h *= 2.0
 
 
@@ -55,8 +60,7 @@ def _occ_eval_host(ss, occ_h):
         return 2
     Z, H, W = occ_h.shape
     if (idx < -np.array([W, H, Z])).any() or (idx >= np.array([W, H, Z])).any():
-        raise _lib.MhError("find_connect_info: a strand indexes outside the occupancy volume (the reference's torch "
-                           "indexing raises IndexError here)")
+        raise _lib.MhError(_OUTSIDE % "find_connect_info: a strand")
     v = occ_h[idx[:, 2], idx[:, 1], idx[:, 0]]
     return 1 if np.float32(v.sum(dtype=np.float32)) / np.float32(v.shape[0]) > np.float32(0.8) else 0
 
@@ -114,9 +118,8 @@ class HairGrowing:
         first_h = np.ascontiguousarray(first.cpu().numpy(), dtype=np.int32)
         ln_h = np.ascontiguousarray(ln.cpu().numpy(), dtype=np.int32)
         seeds_h = np.ascontiguousarray(seeds.cpu().numpy(), dtype=np.float32)
-        lens = np.maximum(ln_h, 0).astype(np.int64)
-        offs_h = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if n else np.zeros(0, np.int64)
-        total = int(lens.sum())
+        offs_h = strand_offsets(np.maximum(ln_h, 0))
+        total = int(offs_h[-1])
         packed = torch.empty((max(total, 1), 3), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mh_strands_compact(self._ctx, _lib.ptr(pts), _lib.ptr(first.contiguous()),
@@ -128,7 +131,7 @@ class HairGrowing:
         acc = np.zeros(n, np.uint8)
         _lib.check(_lib.lib().mh_strands_accept(self.W, self.H, self.Z, _hp(flag), _hp(pts_h), _hp(offs32), _hp(ln_h),
                                                 0, _hp(seeds_h), n, mode, _hp(acc)), "mh_strands_accept")
-        return [pts_h[offs_h[i]:offs_h[i] + ln_h[i]] for i in np.flatnonzero(acc)]
+        return split_strands(pts_h, offs_h, np.flatnonzero(acc))
 
     def _voxel_rounds(self, flag, thrDot, rounds):
         """`rounds` passes of trace() over the occupied voxels.  The reference shifts its seed tensor IN PLACE on
@@ -191,6 +194,95 @@ class HairGrowing:
         self.strands = self._to_device_views(self._voxel_rounds(flag, thrDot, 3))
         return self.strands
 
+    # ------------------------------------------------------------------ find_connect_info, step by step
+    def _end_tables(self, pts, offs, thr):
+        """The four KDTree queries of HairGrow.py:440-470, k = 50 within thr: root->roots, root->tips, tip->roots, tip->tips
+        as (index [N,50], float64 distance, count) on a float64 grid over all 2N ends, binned on the host."""
+        N, dev = len(offs) - 1, self.device
+        ends = np.concatenate([pts[offs[:-1]], pts[offs[1:] - 1]], 0)             # roots, then tips
+        lo = ends.min(0)
+        h, dims = grid_dims(ends.max(0) - lo, thr, 1.0001, 2 * N)
+        cells = np.floor((ends - lo) / h).astype(np.int32)
+        lin = (cells[:, 2].astype(np.int64) * dims[1] + cells[:, 1]) * dims[0] + cells[:, 0]
+        ncell = dims[0] * dims[1] * dims[2]
+        ends_d, qcell_d, grids = [], [], []
+        for t in range(2):          # 0: the roots' tree, 1: the tips'
+            l = lin[t * N:(t + 1) * N]
+            cstart = np.zeros(ncell + 1, np.int32)
+            np.cumsum(np.bincount(l, minlength=ncell), out=cstart[1:])
+            grids.append((_td(np.argsort(l, kind="stable").astype(np.int32), dev), _td(cstart, dev)))
+            ends_d.append(_td(ends[t * N:(t + 1) * N], dev))
+            qcell_d.append(_td(cells[t * N:(t + 1) * N], dev))
+        lists = []
+        for qe, te in ((0, 0), (0, 1), (1, 0), (1, 1)):
+            idx = torch.empty((N, _KNN_K), dtype=torch.int32, device=dev)
+            dist = torch.empty((N, _KNN_K), dtype=torch.float64, device=dev)
+            cnt = torch.empty((N,), dtype=torch.int32, device=dev)
+            _lib.check(_lib.lib().mh_end_knn64(self._ctx, _lib.ptr(ends_d[qe]), _lib.ptr(qcell_d[qe]), N,
+                                               _lib.ptr(ends_d[te]), _lib.ptr(grids[te][0]), _lib.ptr(grids[te][1]),
+                                               dims[0], dims[1], dims[2], thr, 1, _lib.ptr(idx), _lib.ptr(dist),
+                                               _lib.ptr(cnt), _lib.stream_ptr()), "mh_end_knn64")
+            lists.append((idx, dist, cnt))
+        return lists
+
+    def _connect_candidates(self, pts_d, offs_d, N, dot_thr):
+        """find_best_connect_strands (HairGrow.py:550-590) for both ends of every segment -> best, type ([2N] int32)."""
+        arr = lambda k: (ctypes.c_void_p * 4)(*[l[k].data_ptr() for l in self._end_lists])   # noqa: E731
+        best = torch.empty((2 * N,), dtype=torch.int32, device=self.device)
+        btype = torch.empty((2 * N,), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().mh_connect_candidates(self._ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, arr(0), arr(1), arr(2),
+                                                    dot_thr, _lib.ptr(best), _lib.ptr(btype), _lib.stream_ptr()),
+                   "mh_connect_candidates")
+        return best, btype
+
+    def _connect_chains(self, pts_d, offs_d, N, best, btype):
+        """connect_segments (HairGrow.py:303-420): every segment grown along its joins -> (points float64, offsets)."""
+        L, dev = _lib.lib(), self.device
+        total = torch.empty((N,), dtype=torch.int64, device=dev)
+        rootlen = torch.empty((N,), dtype=torch.int64, device=dev)
+        _lib.check(L.mh_chain_count(self._ctx, _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype), _lib.ptr(total),
+                                    _lib.ptr(rootlen), _lib.stream_ptr()), "mh_chain_count")
+        ooffs = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(total, 0, out=ooffs[1:])
+        out = torch.empty((int(ooffs[-1]), 3), dtype=torch.float64, device=dev)
+        _lib.check(L.mh_chain_emit(self._ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype),
+                                   _lib.ptr(rootlen), _lib.ptr(ooffs), _lib.ptr(out), _lib.stream_ptr()), "mh_chain_emit")
+        return out, ooffs
+
+    def _occ_status(self, out, ooffs, N, occ_v):
+        """Attempt 0 of the occupancy test (HairGrow.py:517-528) of every chain on occ_v, a [Z,H,W] view of the volume:
+        int32 [N], 1 accepted, 0 rejected, 2 outside the reference's box, 3 an index torch refuses."""
+        Z, H, W = occ_v.shape
+        status = torch.empty((N,), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().mh_occ_check(self._ctx, _lib.ptr(out), _lib.ptr(ooffs), N, ctypes.c_void_p(occ_v.data_ptr()),
+                                           occ_v.stride(-1), W, H, Z, float(_VMIN64[0]), float(_VMIN64[1]),
+                                           float(_VMIN64[2]), VOXEL_SIZE, _lib.ptr(status), _lib.stream_ptr()),
+                   "mh_occ_check")
+        return status
+
+    def _occ_retries(self, chains, status, occ_v):
+        """The retry loop of HairGrow.py:514-544 for the chains attempt 0 rejected, on the host in segment order with
+        np.random's global generator, exactly as the reference draws -> (strands, number that failed)."""
+        occ_h, fail = None, 0
+        for i, st in enumerate(status):
+            if st == 3:
+                raise _lib.MhError(_OUTSIDE % "find_connect_info: a strand")
+            if st == 0:
+                if occ_h is None:
+                    occ_h = occ_v.cpu().numpy()
+                for count in range(1, 51):
+                    ss = chains[i].copy()
+                    ss += np.random.random((3)) * 0.005
+                    if count >= 50:
+                        break
+                    st = _occ_eval_host(ss, occ_h)
+                    if st == 1:
+                        chains[i] = ss
+                    if st != 0:
+                        break
+            fail += st != 1
+        return chains, int(fail)
+
     def find_connect_info(self, strands, connect_threshold=0.005, connect_dot_threshold=0.7, occ=None):
         """HairGrow.py:434-547: joins the segments (list of float64 [L,3] arrays in world units, L >= 2) into strands and
         returns them.  occ: [1,Z,H,W] occupancy (0/1 values) or None for the solver's own.  The connection table is left
@@ -201,110 +293,94 @@ class HairGrowing:
         self.connect_info, self.connect_fail = [], 0
         if N == 0:
             return []
-        arrs = [np.asarray(s, dtype=np.float64) for s in strands]
-        if any(a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 2 for a in arrs):
-            raise _lib.MhError("find_connect_info: every strand must be [L,3] with L >= 2")
         thr = float(connect_threshold)
         if not (thr > 0 and np.isfinite(thr)):
             raise _lib.MhError("find_connect_info: connect_threshold must be positive and finite")
-        lens = np.array([a.shape[0] for a in arrs], np.int64)
-        offs = np.zeros(N + 1, np.int64)
-        np.cumsum(lens, out=offs[1:])
-        pts = np.ascontiguousarray(np.concatenate(arrs, 0))
-        if not np.isfinite(pts).all():
-            raise _lib.MhError("find_connect_info: non-finite strand points")
-        roots = np.ascontiguousarray(pts[offs[:-1]])
-        tips = np.ascontiguousarray(pts[offs[1:] - 1])
-        cells, dims = _end_cells(np.concatenate([roots, tips], 0), thr)
-        ncell = dims[0] * dims[1] * dims[2]
-        lin = (cells[:, 2].astype(np.int64) * dims[1] + cells[:, 1]) * dims[0] + cells[:, 0]
-        dev, L, ctx = self.device, _lib.lib(), self._ctx
-        td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)    # noqa: E731
-        pts_d, offs_d = td(pts), td(offs)
-        ends_d = [td(roots), td(tips)]
-        qcell_d = [td(cells[:N]), td(cells[N:])]
-        grids = []
-        for t in range(2):          # 0: the roots' tree, 1: the tips'
-            l = lin[t * N:(t + 1) * N]
-            order = np.argsort(l, kind="stable").astype(np.int32)
-            cstart = np.zeros(ncell + 1, np.int32)
-            np.cumsum(np.bincount(l, minlength=ncell), out=cstart[1:])
-            grids.append((td(order), td(cstart)))
-        lists = []
-        with torch.cuda.device(dev):
-            for qe, te in ((0, 0), (0, 1), (1, 0), (1, 1)):   # root->roots, root->tips, tip->roots, tip->tips
-                idx = torch.empty((N, _KNN_K), dtype=torch.int32, device=dev)
-                dist = torch.empty((N, _KNN_K), dtype=torch.float64, device=dev)
-                cnt = torch.empty((N,), dtype=torch.int32, device=dev)
-                _lib.check(L.mh_end_knn64(ctx, _lib.ptr(ends_d[qe]), _lib.ptr(qcell_d[qe]), N, _lib.ptr(ends_d[te]),
-                                          _lib.ptr(grids[te][0]), _lib.ptr(grids[te][1]), dims[0], dims[1], dims[2],
-                                          thr, 1, _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(cnt), _lib.stream_ptr()),
-                           "mh_end_knn64")
-                lists.append((idx, dist, cnt))
-            self._end_lists = lists
-            arr = lambda k: (ctypes.c_void_p * 4)(*[l[k].data_ptr() for l in lists])   # noqa: E731
-            best = torch.empty((2 * N,), dtype=torch.int32, device=dev)
-            btype = torch.empty((2 * N,), dtype=torch.int32, device=dev)
-            _lib.check(L.mh_connect_candidates(ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, arr(0), arr(1), arr(2),
-                                               float(connect_dot_threshold), _lib.ptr(best), _lib.ptr(btype),
-                                               _lib.stream_ptr()), "mh_connect_candidates")
-            total = torch.empty((N,), dtype=torch.int64, device=dev)
-            rootlen = torch.empty((N,), dtype=torch.int64, device=dev)
-            _lib.check(L.mh_chain_count(ctx, _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype), _lib.ptr(total),
-                                        _lib.ptr(rootlen), _lib.stream_ptr()), "mh_chain_count")
-            ooffs = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
-            torch.cumsum(total, 0, out=ooffs[1:])
-            T = int(ooffs[-1])
-            out = torch.empty((T, 3), dtype=torch.float64, device=dev)
-            _lib.check(L.mh_chain_emit(ctx, _lib.ptr(pts_d), _lib.ptr(offs_d), N, _lib.ptr(best), _lib.ptr(btype),
-                                       _lib.ptr(rootlen), _lib.ptr(ooffs), _lib.ptr(out), _lib.stream_ptr()),
-                       "mh_chain_emit")
-            if occ is None:
-                occ_t, ostride = self._vox, 4          # channel 3 of the packed voxels = self.occ
-                Z, H, W = self.Z, self.H, self.W
-                occ_base = occ_t.data_ptr() + 3 * 4
-            else:
-                occ_t = torch.as_tensor(occ).to(dev).float().contiguous()
-                Z, H, W = occ_t.shape[-3:]
-                ostride, occ_base = 1, occ_t[0].data_ptr() if occ_t.dim() == 4 else occ_t.data_ptr()
-            status = torch.empty((N,), dtype=torch.int32, device=dev)
-            _lib.check(L.mh_occ_check(ctx, _lib.ptr(out), _lib.ptr(ooffs), N, ctypes.c_void_p(occ_base), ostride, W, H,
-                                      Z, float(_VMIN64[0]), float(_VMIN64[1]), float(_VMIN64[2]), VOXEL_SIZE,
-                                      _lib.ptr(status), _lib.stream_ptr()), "mh_occ_check")
-            out_h, oo_h, st_h = out.cpu().numpy(), ooffs.cpu().numpy(), status.cpu().numpy()
+        pts, offs = pack_strands(strands, np.float64, "find_connect_info", finite=True)
+        if occ is None:
+            occ_v = self.occ[0]                       # channel 3 of the packed voxels
+        else:
+            occ_v = torch.as_tensor(occ).to(self.device).float().contiguous()
+            occ_v = occ_v.reshape((-1,) + tuple(occ_v.shape[-3:]))[0]
+        with torch.cuda.device(self.device):
+            pts_d, offs_d = _td(pts, self.device), _td(offs, self.device)
+            self._end_lists = self._end_tables(pts, offs, thr)
+            best, btype = self._connect_candidates(pts_d, offs_d, N, float(connect_dot_threshold))
+            out, ooffs = self._connect_chains(pts_d, offs_d, N, best, btype)
+            status = self._occ_status(out, ooffs, N, occ_v).cpu().numpy()
+            chains = split_strands(out.cpu().numpy(), ooffs.cpu().numpy())
             best_h, btype_h = best.cpu().numpy().reshape(N, 2), btype.cpu().numpy().reshape(N, 2)
         self.connect_best, self.connect_best_type = best_h, btype_h
         self.connect_info = [{e: (None if best_h[i, k] < 0 else [int(best_h[i, k]), _TYPES[btype_h[i, k]]])
                               for k, e in enumerate(_TYPES)} for i in range(N)]
-        occ_h = None
-        fail = 0
-        new_strands = []
-        for i in range(N):
-            strand = out_h[oo_h[i]:oo_h[i + 1]]
-            st = int(st_h[i])
-            if st == 3:
-                raise _lib.MhError("find_connect_info: a strand indexes outside the occupancy volume (the reference's "
-                                   "torch indexing raises IndexError here)")
-            if st == 0:           # the retry loop of HairGrow.py:514-544, replayed in segment order
-                if occ_h is None:
-                    occ_h = (self.occ[0] if occ is None else occ_t.reshape(Z, H, W)).cpu().numpy()
-                st = 0
-                for count in range(1, 51):
-                    ss = strand.copy()
-                    ss += np.random.random((3)) * 0.005
-                    if count >= 50:
-                        break
-                    st = _occ_eval_host(ss, occ_h)
-                    if st == 1:
-                        strand = ss
-                        break
-                    if st == 2:
-                        break
-            if st != 1:
-                fail += 1
-            new_strands.append(strand)
-        self.connect_fail = fail
+        new_strands, self.connect_fail = self._occ_retries(chains, status, occ_v)
         return new_strands
+
+    # ------------------------------------------------------------------ connect_to_scalp, step by step
+    def _scalp_core(self, s):
+        """The core set of a pass (HairGrow.py:620-640): the points of the strands rooted so far, the strand of each, and
+        the position of each in KDTree(core).indices -- the order in which query_ball_point returns a ball."""
+        from scipy.spatial import KDTree
+
+        n, dev = s.flags.shape[0], self.device
+        pid = torch.repeat_interleave(torch.arange(n, device=dev), s.offs[1:] - s.offs[:-1])
+        sel = (s.flags[pid] & 1) != 0
+        c = types.SimpleNamespace(pts=s.P[sel].contiguous(), sid=pid[sel].to(torch.int32), grid_thr=None)
+        core_h = c.pts.cpu().numpy()
+        c.M = core_h.shape[0]
+        rank_h = np.empty(c.M, np.int32)
+        rank_h[KDTree(core_h).indices] = np.arange(c.M, dtype=np.int32)
+        c.rank = torch.from_numpy(rank_h).to(dev)
+        c.lo, c.hi = core_h.min(0), core_h.max(0)
+        c.scratch = torch.empty(int(_lib.lib().mh_grid_scratch_bytes(c.M)), dtype=torch.uint8, device=dev)
+        c.order = torch.empty(c.M, dtype=torch.int32, device=dev)
+        return c
+
+    def _scalp_grid(self, c, thr_dist):
+        """The grid of the core points for balls of radius thr_dist: cells a little larger than the radius (the cell of a
+        point is a float32 floor) over the float32 extent."""
+        h, dims = grid_dims((c.hi - c.lo).astype(np.float64), thr_dist, 1.01, c.M)
+        c.grid = np.array([c.lo[0], c.lo[1], c.lo[2], h], np.float32)
+        c.dims = np.array(dims, np.int32)
+        c.cstart = torch.empty(int(np.prod(dims)) + 1, dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().mh_grid_build(self._ctx, _hp(c.grid), _hp(c.dims), _lib.ptr(c.pts), c.M, _lib.ptr(c.scratch),
+                                            c.scratch.numel(), None, _lib.ptr(c.order), _lib.ptr(c.cstart), None,
+                                            _lib.stream_ptr()), "mh_grid_build")
+        c.grid_thr = thr_dist
+
+    def _scalp_pass(self, s, c, act, thr_dist, thr_dot, out_ratio):
+        """One pass of the reference's loop body over the floating strands `act` (the three kernels of
+        csrc/hairscalp.hip); flags, out_ratio, similar, flips and choice of `s` are updated in place.
+        -> (points, offsets after the joins, newly rooted, newly out, strands torch's indexing would refuse)."""
+        L, ctx, dev, st = _lib.lib(), self._ctx, self.device, _lib.stream_ptr()
+        n, nact = s.flags.shape[0], int(act.shape[0])
+        bcnt = torch.empty(nact, dtype=torch.int64, device=dev)
+        _lib.check(L.mh_scalp_ball_count(ctx, _lib.ptr(s.P), _lib.ptr(s.offs), _lib.ptr(act), nact, _lib.ptr(c.pts), c.M,
+                                         _lib.ptr(c.order), _lib.ptr(c.cstart), _hp(c.grid), _hp(c.dims), thr_dist,
+                                         _lib.ptr(bcnt), st), "mh_scalp_ball_count")
+        boff = torch.zeros(nact + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(bcnt, 0, out=boff[1:])
+        bscr = torch.empty(max(int(boff[-1]), 1), dtype=torch.int64, device=dev)
+        flip = torch.zeros(n, dtype=torch.uint8, device=dev)
+        bsid = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        bidx = torch.zeros(n, dtype=torch.int32, device=dev)
+        _lib.check(L.mh_scalp_choose(ctx, _lib.ptr(s.P), _lib.ptr(s.offs), _lib.ptr(act), nact, _lib.ptr(c.pts),
+                                     _lib.ptr(c.sid), _lib.ptr(c.rank), c.M, _lib.ptr(c.order), _lib.ptr(c.cstart),
+                                     _hp(c.grid), _hp(c.dims), thr_dist, thr_dot, _lib.ptr(s.oratio), _lib.ptr(boff),
+                                     _lib.ptr(bscr), _lib.ptr(flip), _lib.ptr(bsid), _lib.ptr(bidx), st), "mh_scalp_choose")
+        joined = bsid >= 0
+        newlen = (s.offs[1:] - s.offs[:-1]) + torch.where(joined, bidx.long() + 1, torch.zeros_like(bidx).long())
+        noffs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(newlen, 0, out=noffs[1:])
+        Pn = torch.empty((int(noffs[-1]), 3), dtype=torch.float32, device=dev)
+        counters = torch.zeros(3, dtype=torch.int32, device=dev)
+        _lib.check(L.mh_scalp_emit(ctx, _lib.ptr(s.P), _lib.ptr(s.offs), n, _lib.ptr(flip), _lib.ptr(bsid), _lib.ptr(bidx),
+                                   _lib.ptr(noffs), _lib.ptr(self._vox), self.W, self.H, self.Z, float(out_ratio),
+                                   _lib.ptr(Pn), _lib.ptr(s.flags), _lib.ptr(s.oratio), _lib.ptr(s.similar),
+                                   _lib.ptr(counters), st), "mh_scalp_emit")
+        s.flips += flip
+        s.choice[joined] = torch.stack([bsid, bidx], 1)[joined]
+        return (Pn, noffs) + tuple(int(v) for v in counters.cpu())
 
     def connect_to_scalp(self, strands, num_root, out_ratio, infer_inner=False):
         """HairGrow.py:606-784: attaches the floating strands (strands[num_root:], float32 [L,3] in voxel units, L >= 2) to
@@ -316,123 +392,48 @@ class HairGrowing:
         pass: thr_dist, thr_dot, rooted and out counts after it), self.scalp_root_flag / scalp_out_flag /
         scalp_out_ratio / scalp_flips (times reversed) / scalp_choice ([n,2]: last neighbour and point index joined, -1
         none) / scalp_similar (random_move_strands' orientation score of that join)."""
-        from scipy.spatial import KDTree
-
-        n = len(strands)
-        arrs = [np.ascontiguousarray(s, dtype=np.float32) for s in strands]
-        if any(a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 2 for a in arrs):
-            raise _lib.MhError("connect_to_scalp: every strand must be [L,3] with L >= 2")
-        num_root = int(num_root)
+        pts_h, offs_h = pack_strands(strands, np.float32, "connect_to_scalp", finite=True)
+        n, num_root, dev = len(strands), int(num_root), self.device
         if n == 0 or num_root <= 0:
             raise _lib.MhError("connect_to_scalp: no rooted strand (the reference's np.concatenate of an empty core list "
                                "raises here)")
-        dev, L, ctx = self.device, _lib.lib(), self._ctx
-        lens = np.array([a.shape[0] for a in arrs], np.int64)
-        offs_h = np.zeros(n + 1, np.int64)
-        np.cumsum(lens, out=offs_h[1:])
-        pts_h = np.concatenate(arrs, 0)
-        if not np.isfinite(pts_h).all():
-            raise _lib.MhError("connect_to_scalp: non-finite strand points")
         flags_h = np.zeros(n, np.uint8)
         flags_h[:num_root] = 1
-        P = torch.from_numpy(pts_h).to(dev)
-        offs = torch.from_numpy(offs_h).to(dev)
-        flags = torch.from_numpy(flags_h).to(dev)
-        oratio = torch.zeros(n, dtype=torch.float64, device=dev)
-        similar = torch.zeros(n, dtype=torch.float32, device=dev)
-        flips = torch.zeros(n, dtype=torch.int32, device=dev)
-        choice = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
-        counters = torch.zeros(3, dtype=torch.int32, device=dev)
+        s = types.SimpleNamespace(P=_td(pts_h, dev), offs=_td(offs_h, dev), flags=_td(flags_h, dev),
+                                  oratio=torch.zeros(n, dtype=torch.float64, device=dev),
+                                  similar=torch.zeros(n, dtype=torch.float32, device=dev),
+                                  flips=torch.zeros(n, dtype=torch.int32, device=dev),
+                                  choice=torch.full((n, 2), -1, dtype=torch.int32, device=dev))
         thr_dist, thr_dot, max_thr_dist, max_dot_dist = 0.5, 0.9, 2.0, 0.6
-        rooted, out_n = num_root, 0
+        rooted, out_n, core = num_root, 0, None       # core: rebuilt when the rooted set has changed
         self.scalp_passes = []
-        core = None           # rebuilt when the rooted set has changed
         with torch.cuda.device(dev):
             while True:
-                act = torch.nonzero(flags == 0)[:, 0].to(torch.int32)
-                nact = int(act.shape[0])
+                act = torch.nonzero(s.flags == 0)[:, 0].to(torch.int32)
                 new_root = new_out = 0
-                if nact:
-                    if core is None:
-                        pid = torch.repeat_interleave(torch.arange(n, device=dev), offs[1:] - offs[:-1])
-                        sel = (flags[pid] & 1) != 0
-                        core = P[sel].contiguous()
-                        csid = pid[sel].to(torch.int32)
-                        core_h = core.cpu().numpy()
-                        M = core_h.shape[0]
-                        rank_h = np.empty(M, np.int32)
-                        rank_h[KDTree(core_h).indices] = np.arange(M, dtype=np.int32)
-                        crank = torch.from_numpy(rank_h).to(dev)
-                        lo, hi = core_h.min(0), core_h.max(0)
-                        scratch = torch.empty(int(L.mh_grid_scratch_bytes(M)), dtype=torch.uint8, device=dev)
-                        order = torch.empty(M, dtype=torch.int32, device=dev)
-                        grid_thr = None
-                    if grid_thr != thr_dist:
-                        # cells a little larger than the radius (the cell of a point is a float32 floor), coarsened
-                        # while there would be more than max(4M, 2^20) of them
-                        h = thr_dist * 1.01
-                        while True:
-                            dims = np.floor((hi - lo).astype(np.float64) / h).astype(np.int64) + 1
-                            if int(np.prod(dims)) <= max(4 * M, 1 << 20):
-                                break
-                            h *= 2.0
-                        grid = np.array([lo[0], lo[1], lo[2], h], np.float32)
-                        dims = dims.astype(np.int32)
-                        cstart = torch.empty(int(np.prod(dims)) + 1, dtype=torch.int32, device=dev)
-                        _lib.check(L.mh_grid_build(ctx, _hp(grid), _hp(dims), _lib.ptr(core), M, _lib.ptr(scratch),
-                                                   scratch.numel(), None, _lib.ptr(order), _lib.ptr(cstart), None,
-                                                   _lib.stream_ptr()), "mh_grid_build")
-                        grid_thr = thr_dist
-                    bcnt = torch.empty(nact, dtype=torch.int64, device=dev)
-                    _lib.check(L.mh_scalp_ball_count(ctx, _lib.ptr(P), _lib.ptr(offs), _lib.ptr(act), nact, _lib.ptr(core),
-                                                     M, _lib.ptr(order), _lib.ptr(cstart), _hp(grid), _hp(dims), thr_dist,
-                                                     _lib.ptr(bcnt), _lib.stream_ptr()), "mh_scalp_ball_count")
-                    boff = torch.zeros(nact + 1, dtype=torch.int64, device=dev)
-                    torch.cumsum(bcnt, 0, out=boff[1:])
-                    bscr = torch.empty(max(int(boff[-1]), 1), dtype=torch.int64, device=dev)
-                    flip = torch.zeros(n, dtype=torch.uint8, device=dev)
-                    bsid = torch.full((n,), -1, dtype=torch.int32, device=dev)
-                    bidx = torch.zeros(n, dtype=torch.int32, device=dev)
-                    _lib.check(L.mh_scalp_choose(ctx, _lib.ptr(P), _lib.ptr(offs), _lib.ptr(act), nact, _lib.ptr(core),
-                                                 _lib.ptr(csid), _lib.ptr(crank), M, _lib.ptr(order), _lib.ptr(cstart),
-                                                 _hp(grid), _hp(dims), thr_dist, thr_dot, _lib.ptr(oratio), _lib.ptr(boff),
-                                                 _lib.ptr(bscr), _lib.ptr(flip), _lib.ptr(bsid), _lib.ptr(bidx),
-                                                 _lib.stream_ptr()), "mh_scalp_choose")
-                    joined = bsid >= 0
-                    newlen = (offs[1:] - offs[:-1]) + torch.where(joined, bidx.long() + 1, torch.zeros_like(bidx).long())
-                    noffs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-                    torch.cumsum(newlen, 0, out=noffs[1:])
-                    Pn = torch.empty((int(noffs[-1]), 3), dtype=torch.float32, device=dev)
-                    counters.zero_()
-                    _lib.check(L.mh_scalp_emit(ctx, _lib.ptr(P), _lib.ptr(offs), n, _lib.ptr(flip), _lib.ptr(bsid),
-                                               _lib.ptr(bidx), _lib.ptr(noffs), _lib.ptr(self._vox), self.W, self.H, self.Z,
-                                               float(out_ratio), _lib.ptr(Pn), _lib.ptr(flags), _lib.ptr(oratio),
-                                               _lib.ptr(similar), _lib.ptr(counters), _lib.stream_ptr()), "mh_scalp_emit")
-                    new_root, new_out, refused = (int(c) for c in counters.cpu())
+                if act.shape[0]:
+                    core = core or self._scalp_core(s)
+                    if core.grid_thr != thr_dist:
+                        self._scalp_grid(core, thr_dist)
+                    s.P, s.offs, new_root, new_out, refused = self._scalp_pass(s, core, act, thr_dist, thr_dot, out_ratio)
                     if refused:
-                        raise _lib.MhError("connect_to_scalp: a joined strand indexes outside the occupancy volume (the "
-                                           "reference's torch indexing raises IndexError here)")
-                    flips += flip
-                    choice[joined] = torch.stack([bsid, bidx], 1)[joined]
-                    P, offs = Pn, noffs
+                        raise _lib.MhError(_OUTSIDE % "connect_to_scalp: a joined strand")
                     if new_root:
                         core = None
                 rooted += new_root
                 out_n += new_out
                 self.scalp_passes.append((thr_dist, thr_dot, rooted, out_n))
-                if not new_root > (n - num_root) // 500:
+                if not new_root > (n - num_root) // 500:     # too few joined: widen the search, or stop at its widest
                     if thr_dist == max_thr_dist and thr_dot == max_dot_dist:
                         break
                     thr_dist = min(thr_dist + 0.25, max_thr_dist)
                     thr_dot = max(thr_dot - 0.075, max_dot_dist)
-            flags_h = flags.cpu().numpy()
-            pts_h, offs_h = P.cpu().numpy(), offs.cpu().numpy()
-            self.scalp_out_ratio = oratio.cpu().numpy()
-            self.scalp_similar = similar.cpu().numpy()
-            self.scalp_flips = flips.cpu().numpy()
-            self.scalp_choice = choice.cpu().numpy()
+            flags_h = s.flags.cpu().numpy()
+            self.scalp_out_ratio, self.scalp_similar = s.oratio.cpu().numpy(), s.similar.cpu().numpy()
+            self.scalp_flips, self.scalp_choice = s.flips.cpu().numpy(), s.choice.cpu().numpy()
+            pts_h, offs_h = s.P.cpu().numpy(), s.offs.cpu().numpy()
         self.scalp_root_flag, self.scalp_out_flag = (flags_h & 1) != 0, (flags_h & 2) != 0
-        return [pts_h[offs_h[i]:offs_h[i + 1]] for i in np.flatnonzero(flags_h)]
+        return split_strands(pts_h, offs_h, np.flatnonzero(flags_h))
 
     def WorldToVoxel(self, strands, bust_to_origin=None):
         """HairGrow.py:826-835 -> list of float32 [L,3] arrays in voxel units (adds bust_to_origin to the caller's arrays
@@ -495,8 +496,7 @@ def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, dev
     bust = np.ascontiguousarray(np.asarray(bust_to_origin, dtype=np.float64).reshape(3))
     dev, L = torch.device(device), _lib.lib()
     ctx = _ctx_for(dev)
-    td = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)    # noqa: E731
-    v_d, vn_d, f_d = td(v), td(vn), td(f.astype(np.int32))
+    v_d, vn_d, f_d = _td(v, dev), _td(vn, dev), _td(f.astype(np.int32), dev)
     area = torch.empty((nf,), dtype=torch.float64, device=dev)
     pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
     nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -506,7 +506,7 @@ def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, dev
                    "mh_tri_area64")
         area_h = area.cpu().numpy()
         B = scalp_allocation(area_h, n)
-        B_d, u_d = td(B), td(u)
+        B_d, u_d = _td(B, dev), _td(u, dev)
         _lib.check(L.mh_mesh_sample(ctx, _lib.ptr(v_d), _lib.ptr(vn_d), nv, _lib.ptr(f_d), nf, _lib.ptr(B_d), _lib.ptr(u_d),
                                     n, _hp(bust), _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(tri), _lib.stream_ptr()),
                    "mh_mesh_sample")
@@ -598,8 +598,6 @@ def diffuse_scalp(save_path, scalp_points_voxel, scalp_normals_voxel, device="cu
     float32 voxel-space points taken back to world units by voxel_to_points, the normals un-flipped (y and z negated
     again) -- and come out as Occ3D_diffusion.mat / Ori3D_diffusion.mat in the same directory, in PMVO.py's layout and
     dtype: get_ground_truth_3D_occ / _ori read back exactly the returned arrays.  Returns (ori [3,Z,Y,X], occ [1,Z,Y,X])."""
-    import os
-
     occ = get_ground_truth_3D_occ(occ_path or os.path.join(save_path, "Occ3D.mat"))          # [Z,Y,X,1]
     ori = get_ground_truth_3D_ori(ori_path or os.path.join(save_path, "Ori3D.mat"))          # [Z,Y,X,3]
     pts = voxel_to_points(torch.as_tensor(scalp_points_voxel).cpu().type(torch.float).clone())
@@ -618,8 +616,6 @@ def generate_segments(occ_path, ori_path, scalp_points_voxel, scalp_normals_voxe
     write_smooth also the Laplacian-smoothed copy scalp_segment_smooth.hair (:914-917).  occ / ori: the readers' arrays
     in place of the two files; solver: a HairGrowing of that volume to use instead of building one.  Returns the unsmoothed
     segments."""
-    import os
-
     if solver is None:
         solver = HairGrowing(occ_path, ori_path, device=device, occ=occ, ori=ori)
     strands, num_root = solver.GenerateGuideStrandFromScalp(scalp_points_voxel, scalp_normals_voxel, None,
@@ -639,8 +635,6 @@ def connect_segments(save_path, bust_to_origin, connect_threshold=0.005, connect
     from save_path, joins the non-root segments (shifted by bust_to_origin) with find_connect_info on the volume of
     occ_path / ori_path (or the arrays occ / ori, or the given solver), smooths every strand (4.0, 2.0) and writes
     strands.hair.  Returns (strands, solver)."""
-    import os
-
     segment, points = load_strand(os.path.join(save_path, "scalp_segment.hair"))
     num_root = int(np.load(os.path.join(save_path, "num_root.npy")))
     bust = np.asarray(bust_to_origin, dtype=np.float64)
@@ -667,8 +661,6 @@ def connect_scalp(save_path, bust_to_origin, out_ratio, occ_path=None, ori_path=
     attaches the floating strands in voxel space (HairGrowing.connect_to_scalp on the volume of occ_path / ori_path or the
     arrays occ / ori, or the given solver), returns to world units, smooths every strand (4.0, 2.0) and writes
     connected_strands.hair.  out_ratio: the case's HairGenerate.out_ratio.  Returns (strands, solver)."""
-    import os
-
     segment, points = load_strand(os.path.join(save_path, "strands.hair"))
     num_root = int(np.load(os.path.join(save_path, "num_root.npy")))
     bust = np.asarray(bust_to_origin, dtype=np.float64)

@@ -11,6 +11,30 @@ from . import _lib
 from .pmvo_utils import _ctx_for
 
 
+def strand_offsets(lens):
+    """int64 [n+1]: where each of n strands of the given lengths starts in their concatenation, and the total."""
+    offs = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(np.asarray(lens, np.int64), out=offs[1:])
+    return offs
+
+
+def pack_strands(strands, dtype, who, finite=False):
+    """The form every strand kernel takes: a list of [L,3] arrays (L >= 2) -> (points [T,3] contiguous in `dtype`, offsets
+    int64 [n+1]).  MhError in the name of the caller `who`; finite: also refuse NaN and infinities."""
+    arrs = [np.asarray(s, dtype=dtype) for s in strands]
+    if any(a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 2 for a in arrs):
+        raise _lib.MhError("%s: every strand must be [L,3] with L >= 2" % who)
+    pts = np.ascontiguousarray(np.concatenate(arrs, 0)) if arrs else np.zeros((0, 3), dtype)
+    if finite and not np.isfinite(pts).all():
+        raise _lib.MhError("%s: non-finite strand points" % who)
+    return pts, strand_offsets([a.shape[0] for a in arrs])
+
+
+def split_strands(pts, offs, which=None):
+    """pack_strands' way back: the strands (all, or those of the indices `which`) as views of pts."""
+    return [pts[offs[i]:offs[i + 1]] for i in (range(len(offs) - 1) if which is None else which)]
+
+
 def smooth_strands(strands, lap_constraint=2.0, pos_constraint=1.0, fix_tips=False, device="cuda:0"):
     """Utils.py:1191-1198: replaces every strands[i] ([L,3], L >= 2) by its smoothed copy, in place on the list (with
     fix_tips, strands[i][1:-1] is overwritten instead), and returns the list."""
@@ -19,24 +43,17 @@ def smooth_strands(strands, lap_constraint=2.0, pos_constraint=1.0, fix_tips=Fal
     if not torch.cuda.is_available():
         raise _lib.MhError("smooth_strands needs a ROCm GPU (no CPU fallback)")
     arrs = [np.asarray(s) for s in strands]
-    lens = np.array([a.shape[0] for a in arrs], np.int64)
-    if lens.min() < 2 or any(a.ndim != 2 or a.shape[1] != 3 for a in arrs):
-        raise _lib.MhError("smooth_strands: every strand must be [L,3] with L >= 2")
-    offs = np.zeros(len(arrs) + 1, np.int64)
-    np.cumsum(lens, out=offs[1:])
     # b[num_pts:] = smoothed_strand[:, axis] * pos_constraint, evaluated in the strand's dtype like the reference
-    rhs = np.concatenate([(a * pos_constraint).astype(np.float64) for a in arrs], 0)
+    rhs, offs = pack_strands([a * pos_constraint for a in arrs], np.float64, "smooth_strands")
     dev = torch.device(device)
-    pts = torch.from_numpy(np.ascontiguousarray(rhs)).to(dev)
+    pts = torch.from_numpy(rhs).to(dev)
     offs_d = torch.from_numpy(offs).to(dev)
     work = torch.empty((3 * int(offs[-1]),), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().mh_smooth_strands(_ctx_for(dev), _lib.ptr(pts), _lib.ptr(offs_d), len(arrs),
                                                 float(lap_constraint), float(pos_constraint), _lib.ptr(work),
                                                 _lib.stream_ptr()), "mh_smooth_strands")
-    sol = pts.cpu().numpy()
-    for i, a in enumerate(arrs):
-        x = sol[offs[i]:offs[i + 1]]
+    for i, (a, x) in enumerate(zip(arrs, split_strands(pts.cpu().numpy(), offs))):
         if fix_tips:
             a[1:-1] = x[1:-1]
             strands[i] = a

@@ -533,3 +533,57 @@ def _assert_sweep_reaches(stats):
     least four segments, a cycle, strands of more than 513 and 1000 points, retries that succeed and that run out"""
     missing = [k for k in _SWEEP_MUST_OCCUR if stats[k] <= 0]
     assert not missing, missing
+
+
+# ------------------------------------------------------------------ the end grid, coarsened
+def _two_clusters(gap):
+    """16 two-point segments in two clusters of 8, the second `gap` away from the first: chains along the diagonal, a tip
+    a fifth of the threshold from the next root, every other segment reversed.  All coordinates are multiples of 2^-20,
+    so every difference and squared distance is exact and moving a cluster changes no distance inside it."""
+    rng = np.random.default_rng(8)
+    u = np.ones(3) / np.sqrt(3.0)
+    segs = []
+    for c in range(2):
+        org = np.array([0.0, -0.02, 0.0]) + c * np.asarray(gap)
+        for k in range(8):
+            a = org + u * (0.004 * k) + rng.normal(scale=1e-4, size=3)
+            s = np.stack([a, a + u * 0.003 + rng.normal(scale=1e-4, size=3)])
+            segs.append(np.round((s[::-1] if k % 2 else s) * 2.0 ** 20) / 2.0 ** 20)
+    return segs
+
+
+def test_end_tables_on_a_doubled_grid(setup):
+    """The doubling branch of grid_dims under mh_end_knn64: with the clusters 1.2 apart the ends' grid would have more
+    than 2^20 cells of the threshold's size and is coarsened; 0.02 apart it is not.  On the coarsened grid the end
+    tables equal the brute-force float64 k-NN (neighbours in adjacent cells among them), and tables and joins are those
+    of the uncoarsened run (same segment order, so the index map is the identity).  The far cluster lies outside the
+    reference's 256 x 256 x 192 box: its strands fail the occupancy test without a retry, which no assertion reads."""
+    from monohair_amd.hairgrow import grid_dims
+
+    _, hg, _, _ = setup
+    thr = 0.005
+    far = np.round(np.array([1.0, -1.0, -1.0]) * (1.2 / np.sqrt(3.0)) * 2.0 ** 20) / 2.0 ** 20
+    near = np.round(np.array([1.0, -1.0, 0.0]) * (0.02 / np.sqrt(2.0)) * 2.0 ** 20) / 2.0 ** 20
+    runs = []
+    for gap in (far, near):
+        segs = _two_clusters(gap)
+        ends = np.concatenate([np.stack([s[0] for s in segs]), np.stack([s[-1] for s in segs])])
+        h, dims = grid_dims(ends.max(0) - ends.min(0), thr, 1.0001, len(ends))
+        cell = np.floor((ends - ends.min(0)) / h).astype(np.int64)
+        np.random.seed(3)
+        hg.find_connect_info([s.copy() for s in segs], thr, 0.7)
+        lists = _np_lists(segs, thr)
+        got, apart = [], 0
+        for k in range(4):
+            idx, dist, cnt = (t.cpu().numpy() for t in hg._end_lists[k])
+            for i in range(16):
+                assert np.array_equal(idx[i, :cnt[i]], lists[k][i][0]) and np.array_equal(dist[i, :cnt[i]], lists[k][i][1])
+                got.append((idx[i, :cnt[i]].tolist(), dist[i, :cnt[i]].tolist()))
+                apart += sum(np.abs(cell[(k // 2) * 16 + i] - cell[(k % 2) * 16 + j]).max() == 1 for j in lists[k][i][0])
+        assert all(((r[0] >= 8) == (i >= 8)).all() for k in range(4) for i, r in enumerate(lists[k]))   # inside a cluster
+        runs.append((h, apart, got, hg.connect_best.copy(), hg.connect_best_type.copy()))
+    (h0, apart0, got0, best0, type0), (h1, _, got1, best1, type1) = runs
+    assert h0 >= 2 * thr * 1.0001 and h1 == thr * 1.0001                 # at least one doubling; none
+    assert apart0 > 0                                                     # neighbours found in an adjacent coarse cell
+    assert sum(len(g[0]) for g in got0) >= 32 and (best0 >= 0).sum() >= 12
+    assert got0 == got1 and np.array_equal(best0, best1) and np.array_equal(type0, type1)

@@ -112,3 +112,84 @@ def test_sweep_inputs_reach_every_situation():
         stats["strand_gt513"] += sum(o.shape[0] > 513 for o in out)
         stats["strand_gt1000"] += sum(o.shape[0] > 1000 for o in out)
     T._assert_sweep_reaches(stats)
+
+
+# ------------------------------------------------------------------ the grid under both neighbour searches
+def _end_cells_rule(ends, bound):
+    """find_connect_info's rule as it stood before grid_dims: float64 ends, slack 1.0001 -> (h, dims)"""
+    lo = ends.min(0)
+    h = bound * 1.0001
+    cap = max(4 * ends.shape[0], 1 << 20)
+    while True:
+        cell = np.floor((ends - lo) / h).astype(np.int64)
+        dims = cell.max(0) + 1
+        if int(np.prod(dims)) <= cap:
+            return h, [int(d) for d in dims]
+        h *= 2.0
+
+
+def _scalp_rule(lo, hi, thr_dist, M):
+    """connect_to_scalp's rule as it stood before grid_dims: float32 extent, slack 1.01 -> (h, dims)"""
+    h = thr_dist * 1.01
+    while True:
+        dims = np.floor((hi - lo).astype(np.float64) / h).astype(np.int64) + 1
+        if int(np.prod(dims)) <= max(4 * M, 1 << 20):
+            break
+        h *= 2.0
+    return h, [int(d) for d in dims]
+
+
+# (extent per axis in units of the radius, number of points, doublings): 2^20 is the cap up to 262144 points, 4n above
+_GRID_CASES = [((90.0, 100.0, 80.0), 1000, 0), ((101.7, 103.2, 102.9), 1000, 1), ((700.0, 650.3, 810.9), 1000, 3),
+               ((256 / 0.505,) * 3, 200000, 3), ((170.2, 160.0, 150.0), 300000, 1), ((105.0, 104.0, 103.0), 300000, 0)]
+
+
+@pytest.mark.parametrize("ext,n,doublings", _GRID_CASES)
+def test_grid_dims_is_both_former_rules(ext, n, doublings):
+    from monohair_amd.hairgrow import grid_dims
+
+    rng = np.random.default_rng(n + doublings)
+    cap = max(4 * n, 1 << 20)
+    # the segment connection: float64 ends (the box corners among them), slack 1.0001
+    r = 0.005
+    ends = np.array([-0.31, 0.07, 0.2]) + rng.random((n, 3)) * (np.array(ext) * r)
+    ends[0], ends[1] = ends.min(0), np.array([-0.31, 0.07, 0.2]) + np.array(ext) * r
+    h, dims = grid_dims(ends.max(0) - ends.min(0), r, 1.0001, n)
+    assert (h, dims) == _end_cells_rule(ends, r)
+    assert h == r * 1.0001 * 2 ** doublings and h >= r * 1.0001 and int(np.prod(dims)) <= cap
+    assert doublings == 0 or int(np.prod(np.floor((ends.max(0) - ends.min(0)) / (h / 2)) + 1)) > cap
+    # the scalp attachment: float32 extent widened, slack 1.01
+    for r in (0.5, 0.75, 2.0):
+        lo = np.array([3.25, 100.1, 17.0], np.float32)
+        hi = (lo + np.array(ext) * r).astype(np.float32)
+        h, dims = grid_dims((hi - lo).astype(np.float64), r, 1.01, n)
+        assert (h, dims) == _scalp_rule(lo, hi, r, n)
+        assert h >= r * 1.01 and int(np.prod(dims)) <= cap and h == r * 1.01 * 2 ** round(np.log2(h / (r * 1.01)))
+    # the production volume at the first radius: 256 voxels / 0.505 per axis is always coarsened
+    assert grid_dims(np.full(3, 256.0), 0.5, 1.01, 1000)[0] > 0.5 * 1.01
+
+
+def test_pack_strands_round_trip_and_refusals():
+    from monohair_amd._lib import MhError
+    from monohair_amd.strand_smooth import pack_strands, split_strands
+
+    rng = np.random.default_rng(3)
+    strands = [rng.random((L, 3)) for L in (2, 7, 3, 64)]
+    for dtype in (np.float64, np.float32):
+        pts, offs = pack_strands(strands, dtype, "caller", finite=True)
+        assert pts.dtype == dtype and pts.flags["C_CONTIGUOUS"] and pts.shape == (76, 3)
+        assert offs.dtype == np.int64 and offs.tolist() == [0, 2, 9, 12, 76]
+        back = split_strands(pts, offs)
+        assert len(back) == 4 and all(np.array_equal(b, s.astype(dtype)) for b, s in zip(back, strands))
+        assert [b.shape[0] for b in split_strands(pts, offs, [3, 1])] == [64, 7]
+    pts, offs = pack_strands([], np.float32, "caller")
+    assert pts.shape == (0, 3) and offs.tolist() == [0] and split_strands(pts, offs) == []
+    for bad in (strands[:1] + [rng.random((1, 3))], strands[:1] + [rng.random((5, 2))], [rng.random(3)]):
+        with pytest.raises(MhError, match="^caller: every strand must be"):
+            pack_strands(bad, np.float64, "caller")
+    nan = [s.copy() for s in strands]
+    nan[2][1, 0] = np.nan
+    with pytest.raises(MhError, match="^caller: non-finite"):
+        pack_strands(nan, np.float64, "caller", finite=True)
+    pts, offs = pack_strands(nan, np.float64, "caller")            # smooth_strands' use: no finite check
+    assert np.isnan(pts[offs[2] + 1, 0]) and np.isfinite(np.delete(pts, offs[2] + 1, 0)).all()

@@ -132,3 +132,64 @@ def test_no_rooted_strand_raises(setup):
         hg.connect_to_scalp([np.zeros((3, 3), np.float32) + np.arange(3, dtype=np.float32)[:, None]], 0, 0.0)
     with pytest.raises(MhError):
         hg.connect_to_scalp([], 0, 0.0)
+
+
+def _face_case(cells):
+    """a rooted strand whose grid at radius 0.5 has `cells` cells along x (1: the extent is below one cell), and floating
+    strands that start exactly on a face of its cells, one float32 below it, and at the grid's origin"""
+    from test_knn_paths_gpu import _first_in_cell
+
+    rng = np.random.default_rng(6)
+    root = (np.array([[100.0, 100.0, 100.0], [100.2, 100.1, 100.0]], np.float32) if cells == 1 else
+            _line([100.0, 100.0, 100.0], [1, 0, 0], 40, rng, 0.25))
+    lo = root.min(0)
+    starts = [lo.copy()]
+    for k in (1,) if cells == 1 else (1, 2, 7):
+        on = np.array([_first_in_cell(lo[0], np.float32(0.505), k), lo[1] + np.float32(0.05), lo[2]], np.float32)
+        starts += [on, np.array([np.nextafter(on[0], np.float32(-np.inf)), on[1], on[2]], np.float32)]
+    floats = []
+    for p in starts:
+        s = _line(p, [3.0, 1.0, 0.2], 4, rng, 3.2)
+        s[0] = p
+        floats.append(s)
+    return [root] + floats, starts
+
+
+@pytest.mark.parametrize("cells", [20, 1])
+def test_ball_of_a_start_on_a_cell_face(setup, cells):
+    """The cell formula under the scalp balls (mh_grid_cell): for strands that start on a cell face of the core grid --
+    in the one-cell grid its far face, where the clamp decides -- one float32 below it and at the origin, the first
+    pass's balls have the size of scipy's query_ball_point, and the attachment (which orders and uses the balls' members)
+    equals the restatement."""
+    import torch
+    import types
+    from scipy.spatial import KDTree
+
+    from monohair_amd import _lib
+    from monohair_amd.hairgrow import _hp, grid_dims
+    from monohair_amd.strand_smooth import pack_strands
+
+    _, _, hg, _, _, vox = setup
+    strands, starts = _face_case(cells)
+    core = strands[0]
+    h, dims = grid_dims((core.max(0) - core.min(0)).astype(np.float64), 0.5, 1.01, len(core))
+    assert np.float32(h) == np.float32(0.505) and dims == [cells, 1, 1]
+    q = np.floor((np.stack(starts)[:, 0] - core.min(0)[0]) / np.float32(h))              # in float32, as the kernel
+    assert q.tolist() == ([0, 1, 0] if cells == 1 else [0, 1, 0, 2, 1, 7, 6])
+    pts, offs = pack_strands(strands, np.float32, "test")
+    flags = np.zeros(len(strands), np.uint8)
+    flags[0] = 1
+    s = types.SimpleNamespace(P=torch.from_numpy(pts).to(DEV), offs=torch.from_numpy(offs).to(DEV),
+                              flags=torch.from_numpy(flags).to(DEV))
+    c = hg._scalp_core(s)
+    hg._scalp_grid(c, 0.5)
+    assert c.dims.tolist() == dims
+    act = torch.arange(1, len(strands), dtype=torch.int32, device=DEV)
+    bcnt = torch.empty(len(starts), dtype=torch.int64, device=DEV)
+    _lib.check(_lib.lib().mh_scalp_ball_count(hg._ctx, _lib.ptr(s.P), _lib.ptr(s.offs), _lib.ptr(act), len(starts),
+                                              _lib.ptr(c.pts), c.M, _lib.ptr(c.order), _lib.ptr(c.cstart), _hp(c.grid),
+                                              _hp(c.dims), 0.5, _lib.ptr(bcnt), _lib.stream_ptr()), "mh_scalp_ball_count")
+    tree = KDTree(core.astype(np.float64))
+    ref = [len(tree.query_ball_point(p.astype(np.float64), 0.5)) for p in starts]
+    assert bcnt.cpu().tolist() == ref and min(ref) >= 1
+    _compare(hg, vox, strands, 1, 0.0)
