@@ -18,12 +18,13 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
 
-def run(out_dir, what=("optimize", "refine", "refine_exact"), device="cuda:0"):
-    import torch
+def golden_pmvo(device="cuda:0"):
+    """(z, meta, pm): the multi-chunk golden file, its meta and a PMVO object on its scene with the toy head set -- the scene
+    of the head-filter golden too (tests/golden/e2e_headfilter.npz)."""
     from scipy.spatial import KDTree
 
     from conftest import GOLDEN, golden_records, golden_scene
-    from monohair_amd.pmvo import PMVO, optimize, refine
+    from monohair_amd.pmvo import PMVO
 
     z = np.load(os.path.join(GOLDEN, "e2e_multichunk.npz"), allow_pickle=False)
     meta = ast.literal_eval(str(z["meta"]))
@@ -33,16 +34,30 @@ def run(out_dir, what=("optimize", "refine", "refine_exact"), device="cuda:0"):
                           visible_threshold=meta["vis_thr"], conf_threshold=meta["thr"])
     scalp = z["toy_scalp"]
     pm.set_head(KDTree(data=z["toy_bust"]), KDTree(data=scalp), np.max(scalp, axis=0))
+    return z, meta, pm
+
+
+def driver_args(root, meta, device="cuda:0"):
+    """The `args` of the drivers with every output under `root` (root/optimize, root/refine)."""
+    a = types.SimpleNamespace(device=device, output_path=root, save_root=os.path.join(root, "optimize"),
+                              save_path=os.path.join(root, "refine"),
+                              PMVO=types.SimpleNamespace(visible_threshold=meta["vis_thr"]),
+                              data=types.SimpleNamespace(root=root))
+    os.makedirs(a.save_path, exist_ok=True)
+    return a
+
+
+def run(out_dir, what=("optimize", "refine", "refine_exact"), device="cuda:0"):
+    import torch
+
+    from conftest import GOLDEN
+    from monohair_amd.pmvo import optimize, refine
+
+    z, meta, pm = golden_pmvo(device)
     fu = z["candidates"][z["filter_index"]]
 
     def args_for(sub):
-        root = os.path.join(out_dir, sub)
-        a = types.SimpleNamespace(device=device, output_path=root, save_root=os.path.join(root, "optimize"),
-                                  save_path=os.path.join(root, "refine"),
-                                  PMVO=types.SimpleNamespace(visible_threshold=meta["vis_thr"]),
-                                  data=types.SimpleNamespace(root=root))
-        os.makedirs(a.save_path, exist_ok=True)
-        return a
+        return driver_args(os.path.join(out_dir, sub), meta, device)
 
     if "pass" in what:
         # the three drivers in sequence on the reference's candidates, arrays handed from one to the next as PMVO.py's caller
