@@ -479,6 +479,38 @@ int mh_diffuse_splat(mh_ctx *ctx, const int32_t *seg_start, const unsigned long 
                      const int32_t *order, const double *unit, int rows, int W, int H, int Z, float *occ, float *ori,
                      void *stream);
 
+/* Strand metrics (monohair_amd.hairmetrics; no counterpart in the reference): point-wise precision / recall of one strand
+ * set against another under joint distance-and-direction bounds.  points [n,3] float32, offsets [n_strands+1] (int64, the
+ * exclusive scan of the per-strand point counts).  float64 arithmetic on the float32 coordinates, + - * / sqrt in the order
+ * written here, nothing fused.
+ * mh_strand_arclen: cum_length[i] (float64 [n]) = length of the strand up to point i, L_i = L_{i-1} + sqrt((dx*dx + dy*dy) +
+ *   dz*dz); n_samples[s] (int64) = floor(L_last / step) + 1, 1 for a strand of one point or of length 0, 0 for an empty one.
+ * mh_strand_resample: sample_offsets [n_strands+1] = exclusive scan of n_samples, n_samples = its last entry.  Sample j of a
+ *   strand sits at arc = j * step on the first segment i with L_{i+1} > arc (when none is, on the last segment of non-zero
+ *   length): u = (arc - L_i) / (L_{i+1} - L_i), q = p_i + u * (p_{i+1} - p_i), rounded to float32.
+ * mh_strand_tangents: d = p[min(i+1, last)] - p[max(i-1, first)], tangents[i] (float64 [n,3]) = d / |d|, valid[i] = 1; 0 and
+ *   valid[i] = 0 where the strand has one point or |d| = 0.
+ * mh_strand_match: out_flags[q] bit k is set iff q_valid[q] and some target has (dx*dx + dy*dy) + dz*dz <= r2[k] and
+ *   |(tx*ux + ty*uy) + tz*uz| >= cos_bound[k] (r2, cos_bound: HOST float64 [n_pairs], n_pairs <= 8).  The targets are the VALID
+ *   targets only, binned by mh_grid_build on a grid (grid_origin_h, grid_dims: HOST) whose cell exceeds the largest radius
+ *   by a slack that covers float32 rounding: t_points_sorted is its pts_sorted, t_tangents_sorted the tangents gathered by its
+ *   order, cell_start its cell_start.  q_order [nq]: a permutation of the queries, mh_grid_build's order of the queries on the
+ *   same grid (it only decides which queries share a wave).  nt >= 1: with no targets every flag is 0 and nothing is to launch.
+ * mh_flag_counts: out9 (uint64 [9]) = per bit k < 8 the number of flag bytes that have it, then the number of non-zero bytes
+ *   of valid. */
+int mh_strand_arclen(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands, double step,
+                     double *cum_length, long long *n_samples, void *stream);
+int mh_strand_resample(mh_ctx *ctx, const float *points, const long long *offsets, const double *cum_length,
+                       const long long *sample_offsets, int n_strands, int n_samples, double step, float *out_points,
+                       void *stream);
+int mh_strand_tangents(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands, int n_points,
+                       double *tangents, uint8_t *valid, void *stream);
+int mh_strand_match(mh_ctx *ctx, const float *q_points, const double *q_tangents, const uint8_t *q_valid,
+                    const int32_t *q_order, int nq, const float *t_points_sorted, const double *t_tangents_sorted, int nt,
+                    const int32_t *cell_start, const float *grid_origin_h, const int32_t *grid_dims, const double *r2,
+                    const double *cos_bound, int n_pairs, uint8_t *out_flags, void *stream);
+int mh_flag_counts(mh_ctx *ctx, const uint8_t *flags, const uint8_t *valid, int n, unsigned long long *out9, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

@@ -73,6 +73,11 @@ _SIGS = {
     "mh_diffuse_walk": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
     "mh_diffuse_arc": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "mh_diffuse_splat": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "mh_strand_arclen": (ci, [vp, vp, vp, ci, ctypes.c_double, vp, vp, vp]),
+    "mh_strand_resample": (ci, [vp, vp, vp, vp, vp, ci, ci, ctypes.c_double, vp, vp]),
+    "mh_strand_tangents": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
+    "mh_strand_match": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]),
+    "mh_flag_counts": (ci, [vp, vp, vp, ci, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

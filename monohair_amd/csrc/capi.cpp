@@ -1192,6 +1192,69 @@ extern "C" int mh_diffuse_splat(mh_ctx *ctx, const int32_t *seg_start, const uns
                     "mh_diffuse_splat");
 }
 
+// ---- strand metrics (csrc/hairmetrics.hip; no counterpart in the reference) -----------------------------------------
+extern "C" int mh_strand_arclen(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands, double step,
+                                double *cum_length, long long *n_samples, void *stream) {
+    if (n_strands == 0) return MH_OK;
+    if (!ctx || !points || !offsets || !cum_length || !n_samples || n_strands < 0 || !(step > 0.0))
+        return fail(MH_ERR_ARG, "mh_strand_arclen: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_arclen(points, (const int64_t *)offsets, n_strands, step, cum_length,
+                                            (int64_t *)n_samples, (hipStream_t)stream),
+                    "mh_strand_arclen");
+}
+
+extern "C" int mh_strand_resample(mh_ctx *ctx, const float *points, const long long *offsets, const double *cum_length,
+                                  const long long *sample_offsets, int n_strands, int n_samples, double step,
+                                  float *out_points, void *stream) {
+    if (n_samples == 0) return MH_OK;
+    if (!ctx || !points || !offsets || !cum_length || !sample_offsets || !out_points || n_strands < 1 || n_samples < 0 ||
+        !(step > 0.0))
+        return fail(MH_ERR_ARG, "mh_strand_resample: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_resample(points, (const int64_t *)offsets, cum_length, (const int64_t *)sample_offsets,
+                                              n_strands, n_samples, step, out_points, (hipStream_t)stream),
+                    "mh_strand_resample");
+}
+
+extern "C" int mh_strand_tangents(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands, int n_points,
+                                  double *tangents, uint8_t *valid, void *stream) {
+    if (n_points == 0) return MH_OK;
+    if (!ctx || !points || !offsets || !tangents || !valid || n_strands < 1 || n_points < 0)
+        return fail(MH_ERR_ARG, "mh_strand_tangents: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_tangents(points, (const int64_t *)offsets, n_strands, n_points, tangents, valid,
+                                              (hipStream_t)stream),
+                    "mh_strand_tangents");
+}
+
+extern "C" int mh_strand_match(mh_ctx *ctx, const float *q_points, const double *q_tangents, const uint8_t *q_valid,
+                               const int32_t *q_order, int nq, const float *t_points_sorted,
+                               const double *t_tangents_sorted, int nt, const int32_t *cell_start, const float *g,
+                               const int32_t *d, const double *r2, const double *cos_bound, int n_pairs, uint8_t *out_flags,
+                               void *stream) {
+    if (nq == 0) return MH_OK;
+    if (!ctx || !q_points || !q_tangents || !q_valid || !q_order || !t_points_sorted || !t_tangents_sorted || !cell_start ||
+        !g || !d || !r2 || !cos_bound || !out_flags || nq < 0 || nt < 1 || n_pairs < 1 || n_pairs > MH_MATCH_MAXK ||
+        !(g[3] > 0.0f) || d[0] < 1 || d[1] < 1 || d[2] < 1 || (long long)d[0] * d[1] * d[2] > 0x7fffffffll)
+        return fail(MH_ERR_ARG, "mh_strand_match: bad arguments");
+    MhMatchPairs pr = {};
+    pr.K = n_pairs;
+    for (int k = 0; k < n_pairs; ++k) pr.r2[k] = r2[k], pr.c[k] = cos_bound[k];
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_match(q_points, q_tangents, q_valid, q_order, nq, t_points_sorted, t_tangents_sorted,
+                                           cell_start, g[0], g[1], g[2], g[3], d[0], d[1], d[2], pr, out_flags,
+                                           (hipStream_t)stream),
+                    "mh_strand_match");
+}
+
+extern "C" int mh_flag_counts(mh_ctx *ctx, const uint8_t *flags, const uint8_t *valid, int n, unsigned long long *out9,
+                              void *stream) {
+    if (!ctx || !out9 || n < 0 || (n > 0 && (!flags || !valid))) return fail(MH_ERR_ARG, "mh_flag_counts: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_flag_counts(flags, valid, n, out9, (hipStream_t)stream), "mh_flag_counts");
+}
+
 static int gabor_alloc(mh_ctx *ctx) {
     if (ctx->gabor) return MH_OK;
     MH_HIP(hipSetDevice(ctx->device));

@@ -32,6 +32,12 @@ struct MhDogWeights {                 // device-resident; w[s][j + r[s]] for j =
     int r[2];
 };
 
+#define MH_MATCH_MAXK 8               // threshold pairs of one mh_strand_match launch: one bit each of the flag byte
+struct MhMatchPairs {                 // pair k: squared distance bound and cosine of the angle bound, both inclusive
+    double r2[MH_MATCH_MAXK], c[MH_MATCH_MAXK];
+    int K;
+};
+
 struct MhRVert;    // raster.hip: a transformed mesh vertex (16 B)
 struct MhRLVert;   // raster.hip: a transformed strand vertex (32 B)
 
@@ -241,4 +247,16 @@ int mh_launch_diffuse_arc(const float *pts, const float *end_pt, const float *fi
 int mh_launch_diffuse_splat(const int32_t *seg_start, const unsigned long long *head_keys, const int32_t *meta,
                             const int32_t *order, const double *unit, int rows, int W, int H, int Z, float *occ, float *ori,
                             hipStream_t st);
+
+// ---- hairmetrics.hip (loads with its first launch)
+int mh_launch_strand_arclen(const float *pts, const int64_t *offs, int S, double step, double *L, int64_t *m,
+                            hipStream_t st);
+int mh_launch_strand_resample(const float *pts, const int64_t *offs, const double *L, const int64_t *soffs, int S,
+                              int total, double step, float *out, hipStream_t st);
+int mh_launch_strand_tangents(const float *pts, const int64_t *offs, int S, int n, double *tan, uint8_t *valid,
+                              hipStream_t st);
+int mh_launch_strand_match(const float *q_pts, const double *q_tan, const uint8_t *q_valid, const int32_t *q_order, int nq,
+                           const float *t_pts, const double *t_tan, const int32_t *cstart, float ox, float oy, float oz,
+                           float h, int dx, int dy, int dz, MhMatchPairs pr, uint8_t *out, hipStream_t st);
+int mh_launch_flag_counts(const uint8_t *flags, const uint8_t *valid, int n, unsigned long long *out9, hipStream_t st);
 }
