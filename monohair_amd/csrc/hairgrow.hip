@@ -4,7 +4,7 @@
 // is one dependent 16-B voxel fetch {ori_x, ori_y, ori_z, occ} (latency bound; tens of thousands of seeds in
 // flight hide it).  The `flag`-volume gate of GenerateGuideStrandFromScalp / randomlyGenerateSegments is
 // sequential over seeds but only decides whether a finished trace is kept, so all seeds are traced in parallel and
-// the gate is replayed afterwards on the host (capi.cpp: mh_strands_accept).
+// the gate is replayed afterwards on the host (capi_host.cpp: mh_strands_accept).
 // Arithmetic as the reference's torch ops: torch.dot of 3-vectors = separately rounded products added left to
 // right, torch.linalg.norm = sqrt of an fma chain, .type(torch.long) = truncation.
 #include "mh_device.h"

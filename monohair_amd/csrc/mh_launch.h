@@ -1,7 +1,7 @@
-// mh_launch.h -- everything that crosses between capi.cpp (the C ABI) and the kernel files: the plain structs that go by
+// mh_launch.h -- everything that crosses between capi*.cpp (the C ABI) and the kernel files: the plain structs that go by
 // value or by layout, the sizes both sides must agree on, and ONE prototype per launcher / preload / size function.
 // Internal (not installed).  Every .hip file sees it through mh_device.h before it defines its launchers, so a definition
-// that disagrees with its declaration does not compile.  No __device__ code here: capi.cpp includes this file alone.
+// that disagrees with its declaration does not compile.  No __device__ code here: capi*.cpp include this file alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,7 +10,7 @@ all and results are bit-identical to the single-GPU run.  Exactly two kinds of e
     ownership is disjoint, every peer sends its slab straight to the root (RCCL send/recv), 1/N of the bytes of a dense
     reduce per link.  Which binding issues those sends is MH_VOLUME_EXCHANGE:
       "torch" (default)  torch.distributed.batch_isend_irecv -- ncclSend/ncclRecv through torch's own RCCL binding;
-      "capi"             mh_volume_gather of the C ABI (librccl bound by hand in csrc/capi.cpp) -- opt-in until it has
+      "capi"             mh_volume_gather of the C ABI (librccl bound by hand in csrc/capi_comm.cpp) -- opt-in until it has
                          run across devices; tested with several ranks sharing one GPU through tests/fake_rccl.cpp;
       "dense"            the dense ncclReduce(sum) of a full volume per rank (x + 0 is exact: the same volume).
     All three give the single-GPU volume bit for bit.

@@ -676,6 +676,17 @@ def _mat5_prefix(name, dims):
     return head + struct.pack("<II", 14, len(body) + ndata + (-ndata % 8)) + body, ndata
 
 
+def _write_mat_sparse(fname, name, dims, idx, val, threads):
+    """one MAT-v5 file holding the float64 array `name` of shape `dims`: zero but for val at the element indices idx"""
+    import ctypes
+
+    prefix, ndata = _mat5_prefix(name, dims)
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    _lib.check(_lib.lib().mh_mat_write_sparse(fname.encode(), prefix, len(prefix), ndata, idx.ctypes.data_as(ctypes.c_void_p),
+                                              val.ctypes.data_as(ctypes.c_void_p), len(idx), threads), "mh_mat_write_sparse")
+
+
 def save_ori_occ_mat_sparse(path, grid_resolution, voxels, ori, threads=1):
     """Same two files as save_ori_occ_mat (PMVO.py:753-764) written from the occupied voxels only: `voxels` [G,3]
     (x,y,z) and `ori` [G,3]; later rows win on duplicates, as the reference's fancy assignments do (:746-747).
@@ -683,53 +694,31 @@ def save_ori_occ_mat_sparse(path, grid_resolution, voxels, ori, threads=1):
     created as a zero-filled sparse file and only the occupied elements are stored (mh_mat_write_sparse: a shared
     mapping; the two files are written concurrently, one thread each -- measured on the GPU box, more threads per file
     only contend for the page cache: 19 ms with one, 34 ms with sixteen, tools/bench_mat.py)."""
-    import ctypes
     from concurrent.futures import ThreadPoolExecutor
 
     X, Y, Z = (int(v) for v in grid_resolution)
     v = np.asarray(voxels, dtype=np.int64).reshape(-1, 3)
     o = np.ascontiguousarray(np.asarray(ori, dtype=np.float64).reshape(-1, 3))
     lin = v[:, 1] + Y * (v[:, 0] + X * v[:, 2])                                # Occ[y,x,z], y fastest
-    L = _lib.lib()
-
-    def write(fname, name, dims, idx, val):
-        prefix, ndata = _mat5_prefix(name, dims)
-        idx = np.ascontiguousarray(idx, dtype=np.int64)
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        _lib.check(L.mh_mat_write_sparse(os.path.join(path, fname).encode(), prefix, len(prefix), ndata,
-                                         idx.ctypes.data_as(ctypes.c_void_p), val.ctypes.data_as(ctypes.c_void_p),
-                                         len(idx), threads), "mh_mat_write_sparse")
-
     jobs = (("Occ3D.mat", "Occ", (Y, X, Z), lin, np.ones(len(v))),
             ("Ori3D.mat", "Ori", (Y, X, 3 * Z), (lin[:, None] + (Y * X * Z) * np.arange(3)[None, :]).reshape(-1),
              o.reshape(-1)))
     with ThreadPoolExecutor(2) as pool:           # ctypes releases the GIL during the call
-        list(pool.map(lambda j: write(*j), jobs))
+        list(pool.map(lambda j: _write_mat_sparse(os.path.join(path, j[0]), *j[1:], threads), jobs))
 
 
 def save_volume_mat_sparse(occ_file, ori_file, occ, ori, threads=1):
     """A dense float32 volume written as the two MAT-v5 files of save_ori_occ_mat (PMVO.py:753-764: Occ [Y,X,Z], Ori
     [Y,X,3Z] with last index c*Z+z, float64) under the given file names, from its non-zero elements only.  occ [Z,Y,X],
     ori [Z,Y,X,3] as the readers return them: get_ground_truth_3D_occ / _ori read back exactly these arrays."""
-    import ctypes
-
     occ = np.asarray(occ, dtype=np.float32)
     ori = np.asarray(ori, dtype=np.float32)
     Z, Y, X = occ.shape
     assert ori.shape == (Z, Y, X, 3)
-    L = _lib.lib()
-
-    def write(fname, name, dims, idx, val):
-        prefix, ndata = _mat5_prefix(name, dims)
-        idx = np.ascontiguousarray(idx, dtype=np.int64)
-        val = np.ascontiguousarray(val, dtype=np.float64)
-        _lib.check(L.mh_mat_write_sparse(fname.encode(), prefix, len(prefix), ndata, idx.ctypes.data_as(ctypes.c_void_p),
-                                         val.ctypes.data_as(ctypes.c_void_p), len(idx), threads), "mh_mat_write_sparse")
-
     z, y, x = np.nonzero(occ)
-    write(occ_file, "Occ", (Y, X, Z), y + Y * (x + X * z), occ[z, y, x])
+    _write_mat_sparse(occ_file, "Occ", (Y, X, Z), y + Y * (x + X * z), occ[z, y, x], threads)
     z, y, x, c = np.nonzero(ori)
-    write(ori_file, "Ori", (Y, X, 3 * Z), y + Y * (x + X * (c * Z + z)), ori[z, y, x, c])
+    _write_mat_sparse(ori_file, "Ori", (Y, X, 3 * Z), y + Y * (x + X * (c * Z + z)), ori[z, y, x, c], threads)
 
 
 class SparseMatWriter:

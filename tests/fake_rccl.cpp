@@ -1,4 +1,4 @@
-// Test-only stand-in for the RCCL entry points libmhpmvo.so binds at run time (monohair_amd/csrc/capi.cpp: rccl_load).
+// Test-only stand-in for the RCCL entry points libmhpmvo.so binds at run time (monohair_amd/csrc/capi_comm.cpp: rccl_load).
 //
 // Why: RCCL refuses two ranks on one device, and the boxes the tests run on have ONE GPU, so the nranks > 1 branches of
 // mh_volume_reduce / mh_volume_gather (group semantics, peer numbers, slab offsets and counts) could never execute there.
@@ -8,7 +8,7 @@
 //
 // What makes it a meaningful check and not a mock that agrees with whatever the caller does:
 //  * it is compiled against <rccl/rccl.h>: every function below has the real header's prototype, so the hand-written
-//    function-pointer types and enum values of capi.cpp are exercised against the real ABI (ncclUniqueId by value,
+//    function-pointer types and enum values of capi_comm.cpp are exercised against the real ABI (ncclUniqueId by value,
 //    ncclFloat32 == 7, ncclSum == 0, argument order);
 //  * NCCL's semantics are enforced where real RCCL would hang or silently corrupt: ncclSend/ncclRecv inside a group are
 //    deferred to ncclGroupEnd, a receive must find a send of exactly the same byte count from exactly that peer, every

@@ -64,3 +64,30 @@ def test_ctypes_stub_of_integration_md():
     pm.Compute_Visible_and_Ori(pts.cpu().numpy())
     assert torch.equal(vis, pm.visible) and torch.equal(ori, pm.Ori) and torch.equal(conf, pm.Conf)
     assert torch.equal(mask, pm.mask) and torch.equal(ori_patch, pm.Ori_patch) and torch.equal(conf_patch, pm.Conf_patch)
+
+
+def search_scratch_table():
+    """(scratch bytes, counts offset) of the search for contexts of V views, N points and a patch side"""
+    from monohair_amd import _lib
+
+    VS, NS, PATCHES = (1, 20, 60, 513), (0, 1, 63, 64, 5000), (1, 5, 9)
+    L = _lib.lib()
+    out = np.zeros((len(VS), len(NS), len(PATCHES), 2), dtype=np.uint64)
+    for i, V in enumerate(VS):
+        ctx = ctypes.c_void_p()
+        _lib.check(L.mh_ctx_create(0, ctypes.byref(ctx)), "mh_ctx_create")
+        _lib.check(L.mh_ctx_alloc_views(ctx, V, 1, 1), "mh_ctx_alloc_views")
+        for j, N in enumerate(NS):
+            for k, patch in enumerate(PATCHES):
+                out[i, j, k] = (L.mh_search_scratch_bytes(ctx, N, patch), L.mh_search_counts_offset(ctx, N, patch))
+        L.mh_ctx_destroy(ctx)
+    return out
+
+
+def test_search_scratch_layout_is_the_recorded_one():
+    """The drivers size and slice the search scratch by these two numbers and the kernels read past list ends by design, so
+    a layout that moves corrupts silently.  tests/golden/search_scratch_layout.npy holds the layout of the single-file C ABI
+    layer, before its split into translation units; regenerate it, with np.save of search_scratch_table(), only with a
+    deliberate layout change."""
+    want = np.load(os.path.join(ROOT, "tests", "golden", "search_scratch_layout.npy"))
+    assert np.array_equal(search_scratch_table(), want)

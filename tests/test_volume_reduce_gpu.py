@@ -4,7 +4,7 @@
   * tests/fake_rccl.cpp bound through MH_RCCL_LIB, 2 and 3 ranks SHARING the one GPU: the nranks > 1 branches -- grouped
     send/recv, peer numbers, slab offsets and counts, uneven and empty slabs, a root other than 0 -- assembled volume
     compared bit for bit; and monohair_amd.dist.voxel_fit_reduced with MH_VOLUME_EXCHANGE=capi against the single-process
-    fit.  The stand-in is compiled against <rccl/rccl.h>, so the hand-written prototypes in capi.cpp meet the real ABI;
+    fit.  The stand-in is compiled against <rccl/rccl.h>, so the hand-written prototypes in capi_comm.cpp meet the real ABI;
   * with two or more GPUs the real exchange runs as well (skips on a one-GPU box -- the only skip of the suite)."""
 import os
 import subprocess
