@@ -25,10 +25,10 @@ extern "C" int mh_ctx_create(int device_id, mh_ctx **out) {
     // the code objects of the library go onto the device now (HIP would load each translation unit's on the first launch
     // of one of its kernels -- in the middle of the first pass's stages); a failure here only means they load lazily
     if (hipSetDevice(device_id) == hipSuccess) {
-        int (*const preload[])() = {mh_preload_pmvo_project, mh_preload_pmvo_search, mh_preload_pmvo_filter,
-                                    mh_preload_consensus,    mh_preload_gabor,       mh_preload_hairgrow,
-                                    mh_preload_knn,          mh_preload_raster,      mh_preload_sortgroup,
-                                    mh_preload_pmvo_pieces,  mh_preload_dog};
+        int (*const preload[])() = {mh_preload_pmvo_project, mh_preload_pmvo_search, mh_preload_pmvo_refine,
+                                    mh_preload_pmvo_filter,  mh_preload_consensus,   mh_preload_gabor,
+                                    mh_preload_hairgrow,     mh_preload_knn,         mh_preload_raster,
+                                    mh_preload_sortgroup,    mh_preload_pmvo_pieces, mh_preload_dog};
         for (auto f : preload) (void)f();
         (void)hipGetLastError();
     }

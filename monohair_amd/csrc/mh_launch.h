@@ -93,6 +93,9 @@ int mh_launch_search(MhViews vw, const float *offs, int S, int nrank, int rank_s
                      int32_t *best_s, MhSearchPlan plan, int rule_mode, int fma_min_cols, int sum_block,
                      int32_t *gcnt /* MH_GROUP_COPIES * MH_GROUP_RANKS * V ints of work space */,
                      int groups_ready /* gcnt holds the batch's group sizes already (the fused forward) */, hipStream_t st);
+int mh_preload_pmvo_search();
+
+// ---- pmvo_refine.hip (the losses of PMVO.refine and of its smoothing loop)
 int mh_launch_refine_loss_maps(MhViews vw, const float *pts, const float *dir, float mul, float dv, int N, int patch,
                                float thr, float *loss, uint8_t *hc, int batch, long long row0, long long total,
                                int sum_block, hipStream_t st);
@@ -101,7 +104,7 @@ int mh_launch_refine_combine(const float *center, const float *loss_u, const uin
 int mh_launch_refine_loss(MhViews vw, const float *pts, const float *dir, float mul, float dv, int N, int P, float thr,
                           const float *vis, const float *ori_patch, const float *conf_patch, float *loss, uint8_t *hc,
                           int sum_block, hipStream_t st);
-int mh_preload_pmvo_search();
+int mh_preload_pmvo_refine();
 
 // ---- pmvo_filter.hip
 int mh_launch_filter_points(MhViews vw, const float *pts, int N, int patch, float thr, float vis_thr,

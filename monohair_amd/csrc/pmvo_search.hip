@@ -16,168 +16,17 @@
 // a four-tap block (see mh_key_walked).
 // Views in which the point is not visible (vis == -1 => weight 0, PMVO.py:212) are skipped: adding
 // their exact zeros would not change any sum.
-#include "mh_device.h"
+#include "mh_search_common.h"
 #include "../../include/mh_pmvo_lab.h"   // mh_debug_key_stats
 
-#define MH_MAX_ITEMS 1024
-#define MH_MAX_RANKS 16
-
-// PMVO.sample_next_3d_pos for one item: pixel(unrounded) + 2*(ori_col, ori_row) -> ndc -> unproject
+// PMVO.sample_next_3d_pos for one item from scratch: rank part + item part (mh_search_common.h).  Only the portable kernel
+// uses it; the shipped one evaluates the rank part once per (point, rank) and keeps it in LDS.
 __device__ __forceinline__ void mh_sample_next(const float *__restrict__ cam, float X0, float X1, float X2,
                                                float ori_r, float ori_c, float Hf, float Wf, float off, float &S0,
-                                               float &S1, float &S2, int forms = 0) {
-    float u, v, z, row, col;
-    if (forms & MH_FORM_GEMV) mh_cam_project_single(cam, X0, X1, X2, u, v, z);
-    else mh_cam_project(cam, X0, X1, X2, u, v, z);
-    mh_ndc_to_pixel(u, v, Hf, Wf, row, col);
-    float nx = col + ori_c * 2.0f;
-    float ny = row + ori_r * 2.0f;
-    nx = nx / Wf;
-    ny = ny / Hf;
-    nx = nx * 2.0f - 1.0f;
-    ny = ny * 2.0f - 1.0f;
-    nx = -nx;
-    mh_cam_unproject(cam, nx, ny, z + off, S0, S1, S2, (forms & MH_FORM_CHAIN) != 0);
-}
-
-// mh_sample_next split at what the S samples of one base-view rank have in common (the point's pixel in the base view, the
-// shifted pixel in NDC, the two quotients of mh_cam_unproject) and what is per sample (depth + offset onwards).  Same
-// operations on the same values in the same order, so rank part + item part == mh_sample_next bit for bit; the shipped
-// search evaluates the rank part once per (point, rank) instead of once per item (90 times) and keeps it in LDS.
-// rec[16] = { A, B, z, t0 | t1, t2, Ri0, Ri1 | Ri2 .. Ri5 | Ri6, Ri7, Ri8, forms }
-// forms (mh_group_forms): how the sgemms of this (rank, base view) group round in the reference -- MH_FORM_GEMV here,
-// MH_FORM_CHAIN in the item part.
-__device__ __forceinline__ void mh_sample_rank(const float *__restrict__ cam, float X0, float X1, float X2, float ori_r,
-                                               float ori_c, float Hf, float Wf, float *__restrict__ rec, int forms = 0) {
-    float u, v, z, row, col;
-    if (forms & MH_FORM_GEMV) mh_cam_project_single(cam, X0, X1, X2, u, v, z);
-    else mh_cam_project(cam, X0, X1, X2, u, v, z);
-    mh_ndc_to_pixel(u, v, Hf, Wf, row, col);
-    float nx = col + ori_c * 2.0f;
-    float ny = row + ori_r * 2.0f;
-    nx = nx / Wf;
-    ny = ny / Hf;
-    nx = nx * 2.0f - 1.0f;
-    ny = ny * 2.0f - 1.0f;
-    nx = -nx;
-    rec[0] = (nx - cam[18]) / cam[16];
-    rec[1] = (ny - cam[22]) / cam[21];
-    rec[2] = z;
-    rec[3] = cam[3];
-    rec[4] = cam[7];
-    rec[5] = cam[11];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rec[6 + i] = cam[32 + i];
-    rec[15] = __int_as_float(forms);
-}
-
-__device__ __forceinline__ void mh_sample_item(const float4 *__restrict__ rec, float off, float &S0, float &S1, float &S2) {
-    const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
-    const float z = a.z + off;
-    const float c0 = a.x * z, c1 = a.y * z;
-    const float d0 = c0 - a.w, d1 = c1 - b.x, d2 = z - b.y;
-    if (__float_as_int(d.w) & MH_FORM_CHAIN) {   // (prologue / epilogue only: once per item)
-        S0 = mh_fma(c.x, d2, mh_fma(b.w, d1, b.z * d0));
-        S1 = mh_fma(c.w, d2, mh_fma(c.z, d1, c.y * d0));
-        S2 = mh_fma(d.z, d2, mh_fma(d.y, d1, d.x * d0));
-    } else {
-        S0 = (b.z * d0 + c.x * d2) + b.w * d1;
-        S1 = (c.y * d0 + c.w * d2) + c.z * d1;
-        S2 = (d.x * d0 + d.z * d2) + d.y * d1;
-    }
-}
-
-// where the trailing columns of the batch's [V, N*S] sums fall in point n: its first trailing sample (S if none)
-__device__ __forceinline__ int mh_tail_from(const MhRule &rule, int n, int S) {
-    const long long c0 = (long long)n * S;
-    if (c0 + S <= rule.tail_col0) return S;
-    return c0 >= rule.tail_col0 ? 0 : (int)(rule.tail_col0 - c0);
-}
-
-// The weighted sums over the views of ONE candidate (item position X) of point n in ATen's row_sum order (mh_device.h:
-// mh_row_sum_views) -- for the trailing columns of the batch's [V, N*S] sums.  The per-view terms are evaluated as the
-// portable kernel evaluates them (same operations as the shipped bodies, bit for bit): tap lists from the scratch records,
-// views that do not see the point (list length 0) add +0; cnt = the number of views with a positive weight.  It runs for a few
-// dozen items per launch, after the view loops, from the item's rank record in LDS -- nothing of it is live in those loops
-// (inside mh_search_slices_lds the same code cost the hot kernel 20 spilled registers).
-__device__ __forceinline__ void mh_tail_item_sums(const float *__restrict__ cams, int V, float Hf, float Wf,
-                                                  const float4 *__restrict__ taps_n, size_t vstride,
-                                                  const uint8_t *__restrict__ vcnt_n, int N, float X0, float X1, float X2,
-                                                  float &nm_out, float &dn_out, int &cnt_out) {
-    int cnt = 0;
-    auto term = [&](int v, float &tn, float &td) {
-        tn = td = 0.0f;
-        const int ntap = vcnt_n ? (int)vcnt_n[(size_t)v * N] : -1;
-        if (ntap == 0) return;
-        const float4 *__restrict__ rec = taps_n + (size_t)v * vstride;
-        const float4 hdr = rec[0];
-        if (hdr.y == -1.0f) return;
-        const int nt = ntap > 0 ? ntap : __float_as_int(hdr.x);
-        float row, col, dx, dy;
-        mh_pixel_of(cams + v * MH_CAM_STRIDE, X0, X1, X2, Hf, Wf, row, col);
-        mh_unit2(row - hdr.z, col - hdr.w, dx, dy);
-        const float4 t0 = rec[1];
-        float ml = 1.0f - __builtin_fabsf(t0.x * dx + t0.y * dy), bc = t0.z;
-#pragma unroll 4
-        for (int t = 1; t < nt; ++t) {
-            const float4 tp = rec[1 + t];
-            const float l = 1.0f - __builtin_fabsf(tp.x * dx + tp.y * dy);
-            const bool upd = l < ml;
-            ml = upd ? l : ml;
-            bc = upd ? tp.z : bc;
-        }
-        tn = ml * bc;
-        td = bc;
-        cnt += (bc > 0.0f) ? 1 : 0;
-    };
-    const int L = V >> 2;
-    float pn[4][3] = {}, pd[4][3] = {};   // partial k (rows k, k+4, ...): cascade levels 0, 1, 2
-    for (int i = 0; i < L; ++i) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float tn, td;
-            term(4 * i + k, tn, td);
-            pn[k][0] = pn[k][0] + tn;
-            pd[k][0] = pd[k][0] + td;
-        }
-        if (((i + 1) & 15) == 0) {   // a full block of 16 rows per partial: level 0 -> 1, every 256 rows level 1 -> 2
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                pn[k][1] = pn[k][1] + pn[k][0];
-                pn[k][0] = 0.0f;
-                pd[k][1] = pd[k][1] + pd[k][0];
-                pd[k][0] = 0.0f;
-                if (((i + 1) & 0xF0) == 0) {
-                    pn[k][2] = pn[k][2] + pn[k][1];
-                    pn[k][1] = 0.0f;
-                    pd[k][2] = pd[k][2] + pd[k][1];
-                    pd[k][1] = 0.0f;
-                }
-            }
-        }
-    }
-    float sn[4], sd[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sn[k] = (pn[k][0] + pn[k][1]) + pn[k][2];
-        sd[k] = (pd[k][0] + pd[k][1]) + pd[k][2];
-    }
-    for (int v = L * 4; v < V; ++v) {
-        float tn, td;
-        term(v, tn, td);
-        sn[0] = sn[0] + tn;
-        sd[0] = sd[0] + td;
-    }
-    nm_out = ((sn[0] + sn[1]) + sn[2]) + sn[3];
-    dn_out = ((sd[0] + sd[1]) + sd[2]) + sd[3];
-    cnt_out = cnt;
-}
-
-// torch.min over a row with NaN propagation: NaN beats numbers, first index wins among equals
-__device__ __forceinline__ bool mh_min_better(float al, int ai, float bl, int bi) {
-    const bool an = al != al, bn = bl != bl;
-    if (an || bn) return (an && bn) ? (ai < bi) : an;
-    return (al < bl) || (al == bl && ai < bi);
+                                               float &S1, float &S2, int forms) {
+    alignas(16) float rec[16];
+    mh_sample_rank(cam, X0, X1, X2, ori_r, ori_c, Hf, Wf, rec, forms);
+    mh_sample_item(reinterpret_cast<const float4 *>(rec), off, S0, S1, S2);
 }
 
 // 1 - |x| as ONE instruction (abs is a source modifier); kept out of the SLP vectoriser's reach
@@ -534,261 +383,12 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
 // the compiler as one asm statement per instruction, its hazard recogniser pads every inline-asm result that is read by
 // the very next instruction with an s_nop -- it cannot see that no dst_sel is involved: ~9 per block.)  The "memory"
 // clobber keeps the LDS reads of the NEXT tap group, issued in front of the block, in front of it.
-// (The four bodies below are printed by tools/gen_key_blocks.py.)
+// (mh_key_blocks.h is written by tools/gen_key_blocks.py; tests/test_host.py compares the two.)
 // Taps g[0], g[2] (places ib, ib + 1 among the even taps) go into ke, taps g[1], g[3] (the same places among the odd taps)
 // into ko; the first NI entries of the caller's arrays are used.  (Padding lists to two taps instead of four, with a
 // two-tap block for the tail, was measured: the choice between two asm blocks that update the same registers costs eight
 // register copies and a wait for every LDS read per call -- 0.634 instead of 0.582 ms.)
-template <int NI, int KN>
-__device__ __forceinline__ void mh_key_block4(unsigned (&ke)[KN], unsigned (&ko)[KN], const float2 (&g)[4],
-                                              const float (&DX)[KN], const float (&DY)[KN], int ib) {
-    static_assert(NI >= 1 && NI <= 4 && NI <= KN, "mh_key_block4: 1..4 items");
-    float a[NI], b[NI], c[NI];
-    if constexpr (NI == 4) {
-        asm volatile(
-            "v_mul_f32_e32 %[a0], %[t0x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t0x], %[x1]\n\t"
-            "v_mul_f32_e32 %[a2], %[t0x], %[x2]\n\t"
-            "v_mul_f32_e32 %[a3], %[t0x], %[x3]\n\t"
-            "v_mul_f32_e32 %[b0], %[t0y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t0y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t0y], %[y2]\n\t"
-            "v_mul_f32_e32 %[b3], %[t0y], %[y3]\n\t"
-            "v_mul_f32_e32 %[c0], %[t2x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t2x], %[x1]\n\t"
-            "v_mul_f32_e32 %[c2], %[t2x], %[x2]\n\t"
-            "v_mul_f32_e32 %[c3], %[t2x], %[x3]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_add_f32_e32 %[a2], %[a2], %[b2]\n\t"
-            "v_add_f32_e32 %[a3], %[a3], %[b3]\n\t"
-            "v_mul_f32_e32 %[b0], %[t2y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t2y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t2y], %[y2]\n\t"
-            "v_mul_f32_e32 %[b3], %[t2y], %[y3]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_sub_f32_e64 %[a2], %[cc], |%[a2]|\n\t"
-            "v_sub_f32_e64 %[a3], %[cc], |%[a3]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_add_f32_e32 %[c2], %[c2], %[b2]\n\t"
-            "v_add_f32_e32 %[c3], %[c3], %[b3]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a2], %[a2], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a3], %[a3], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_sub_f32_e64 %[c2], %[cc], |%[c2]|\n\t"
-            "v_sub_f32_e64 %[c3], %[cc], |%[c3]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c2], %[c2], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c3], %[c3], 5, %[i1]\n\t"
-            "v_min3_u32 %[e0], %[e0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[e1], %[e1], %[a1], %[c1]\n\t"
-            "v_min3_u32 %[e2], %[e2], %[a2], %[c2]\n\t"
-            "v_min3_u32 %[e3], %[e3], %[a3], %[c3]\n\t"
-            "v_mul_f32_e32 %[a0], %[t1x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t1x], %[x1]\n\t"
-            "v_mul_f32_e32 %[a2], %[t1x], %[x2]\n\t"
-            "v_mul_f32_e32 %[a3], %[t1x], %[x3]\n\t"
-            "v_mul_f32_e32 %[b0], %[t1y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t1y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t1y], %[y2]\n\t"
-            "v_mul_f32_e32 %[b3], %[t1y], %[y3]\n\t"
-            "v_mul_f32_e32 %[c0], %[t3x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t3x], %[x1]\n\t"
-            "v_mul_f32_e32 %[c2], %[t3x], %[x2]\n\t"
-            "v_mul_f32_e32 %[c3], %[t3x], %[x3]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_add_f32_e32 %[a2], %[a2], %[b2]\n\t"
-            "v_add_f32_e32 %[a3], %[a3], %[b3]\n\t"
-            "v_mul_f32_e32 %[b0], %[t3y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t3y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t3y], %[y2]\n\t"
-            "v_mul_f32_e32 %[b3], %[t3y], %[y3]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_sub_f32_e64 %[a2], %[cc], |%[a2]|\n\t"
-            "v_sub_f32_e64 %[a3], %[cc], |%[a3]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_add_f32_e32 %[c2], %[c2], %[b2]\n\t"
-            "v_add_f32_e32 %[c3], %[c3], %[b3]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a2], %[a2], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a3], %[a3], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_sub_f32_e64 %[c2], %[cc], |%[c2]|\n\t"
-            "v_sub_f32_e64 %[c3], %[cc], |%[c3]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c2], %[c2], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c3], %[c3], 5, %[i1]\n\t"
-            "v_min3_u32 %[o0], %[o0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[o1], %[o1], %[a1], %[c1]\n\t"
-            "v_min3_u32 %[o2], %[o2], %[a2], %[c2]\n\t"
-            "v_min3_u32 %[o3], %[o3], %[a3], %[c3]"
-            : [e0] "+v"(ke[0]), [e1] "+v"(ke[1]), [e2] "+v"(ke[2]), [e3] "+v"(ke[3]), [o0] "+v"(ko[0]), [o1] "+v"(ko[1]), [o2] "+v"(ko[2]), [o3] "+v"(ko[3]), [a0] "=&v"(a[0]), [a1] "=&v"(a[1]), [a2] "=&v"(a[2]), [a3] "=&v"(a[3]), [b0] "=&v"(b[0]), [b1] "=&v"(b[1]), [b2] "=&v"(b[2]), [b3] "=&v"(b[3]), [c0] "=&v"(c[0]), [c1] "=&v"(c[1]), [c2] "=&v"(c[2]), [c3] "=&v"(c[3])
-            : [t0x] "v"(g[0].x), [t0y] "v"(g[0].y), [t1x] "v"(g[1].x), [t1y] "v"(g[1].y), [t2x] "v"(g[2].x), [t2y] "v"(g[2].y), [t3x] "v"(g[3].x), [t3y] "v"(g[3].y), [x0] "v"(DX[0]), [y0] "v"(DY[0]), [x1] "v"(DX[1]), [y1] "v"(DY[1]), [x2] "v"(DX[2]), [y2] "v"(DY[2]), [x3] "v"(DX[3]), [y3] "v"(DY[3]), [cc] "s"(MH_KEY_C), [i0] "s"(ib), [i1] "s"(ib + 1)
-            : "memory");
-    }
-    else if constexpr (NI == 3) {
-        asm volatile(
-            "v_mul_f32_e32 %[a0], %[t0x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t0x], %[x1]\n\t"
-            "v_mul_f32_e32 %[a2], %[t0x], %[x2]\n\t"
-            "v_mul_f32_e32 %[b0], %[t0y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t0y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t0y], %[y2]\n\t"
-            "v_mul_f32_e32 %[c0], %[t2x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t2x], %[x1]\n\t"
-            "v_mul_f32_e32 %[c2], %[t2x], %[x2]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_add_f32_e32 %[a2], %[a2], %[b2]\n\t"
-            "v_mul_f32_e32 %[b0], %[t2y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t2y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t2y], %[y2]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_sub_f32_e64 %[a2], %[cc], |%[a2]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_add_f32_e32 %[c2], %[c2], %[b2]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a2], %[a2], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_sub_f32_e64 %[c2], %[cc], |%[c2]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c2], %[c2], 5, %[i1]\n\t"
-            "v_min3_u32 %[e0], %[e0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[e1], %[e1], %[a1], %[c1]\n\t"
-            "v_min3_u32 %[e2], %[e2], %[a2], %[c2]\n\t"
-            "v_mul_f32_e32 %[a0], %[t1x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t1x], %[x1]\n\t"
-            "v_mul_f32_e32 %[a2], %[t1x], %[x2]\n\t"
-            "v_mul_f32_e32 %[b0], %[t1y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t1y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t1y], %[y2]\n\t"
-            "v_mul_f32_e32 %[c0], %[t3x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t3x], %[x1]\n\t"
-            "v_mul_f32_e32 %[c2], %[t3x], %[x2]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_add_f32_e32 %[a2], %[a2], %[b2]\n\t"
-            "v_mul_f32_e32 %[b0], %[t3y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t3y], %[y1]\n\t"
-            "v_mul_f32_e32 %[b2], %[t3y], %[y2]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_sub_f32_e64 %[a2], %[cc], |%[a2]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_add_f32_e32 %[c2], %[c2], %[b2]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a2], %[a2], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_sub_f32_e64 %[c2], %[cc], |%[c2]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c2], %[c2], 5, %[i1]\n\t"
-            "v_min3_u32 %[o0], %[o0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[o1], %[o1], %[a1], %[c1]\n\t"
-            "v_min3_u32 %[o2], %[o2], %[a2], %[c2]"
-            : [e0] "+v"(ke[0]), [e1] "+v"(ke[1]), [e2] "+v"(ke[2]), [o0] "+v"(ko[0]), [o1] "+v"(ko[1]), [o2] "+v"(ko[2]), [a0] "=&v"(a[0]), [a1] "=&v"(a[1]), [a2] "=&v"(a[2]), [b0] "=&v"(b[0]), [b1] "=&v"(b[1]), [b2] "=&v"(b[2]), [c0] "=&v"(c[0]), [c1] "=&v"(c[1]), [c2] "=&v"(c[2])
-            : [t0x] "v"(g[0].x), [t0y] "v"(g[0].y), [t1x] "v"(g[1].x), [t1y] "v"(g[1].y), [t2x] "v"(g[2].x), [t2y] "v"(g[2].y), [t3x] "v"(g[3].x), [t3y] "v"(g[3].y), [x0] "v"(DX[0]), [y0] "v"(DY[0]), [x1] "v"(DX[1]), [y1] "v"(DY[1]), [x2] "v"(DX[2]), [y2] "v"(DY[2]), [cc] "s"(MH_KEY_C), [i0] "s"(ib), [i1] "s"(ib + 1)
-            : "memory");
-    }
-    else if constexpr (NI == 2) {
-        asm volatile(
-            "v_mul_f32_e32 %[a0], %[t0x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t0x], %[x1]\n\t"
-            "v_mul_f32_e32 %[b0], %[t0y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t0y], %[y1]\n\t"
-            "v_mul_f32_e32 %[c0], %[t2x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t2x], %[x1]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_mul_f32_e32 %[b0], %[t2y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t2y], %[y1]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_min3_u32 %[e0], %[e0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[e1], %[e1], %[a1], %[c1]\n\t"
-            "v_mul_f32_e32 %[a0], %[t1x], %[x0]\n\t"
-            "v_mul_f32_e32 %[a1], %[t1x], %[x1]\n\t"
-            "v_mul_f32_e32 %[b0], %[t1y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t1y], %[y1]\n\t"
-            "v_mul_f32_e32 %[c0], %[t3x], %[x0]\n\t"
-            "v_mul_f32_e32 %[c1], %[t3x], %[x1]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_add_f32_e32 %[a1], %[a1], %[b1]\n\t"
-            "v_mul_f32_e32 %[b0], %[t3y], %[y0]\n\t"
-            "v_mul_f32_e32 %[b1], %[t3y], %[y1]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_sub_f32_e64 %[a1], %[cc], |%[a1]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_add_f32_e32 %[c1], %[c1], %[b1]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_lshl_or_b32 %[a1], %[a1], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_sub_f32_e64 %[c1], %[cc], |%[c1]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_lshl_or_b32 %[c1], %[c1], 5, %[i1]\n\t"
-            "v_min3_u32 %[o0], %[o0], %[a0], %[c0]\n\t"
-            "v_min3_u32 %[o1], %[o1], %[a1], %[c1]"
-            : [e0] "+v"(ke[0]), [e1] "+v"(ke[1]), [o0] "+v"(ko[0]), [o1] "+v"(ko[1]), [a0] "=&v"(a[0]), [a1] "=&v"(a[1]), [b0] "=&v"(b[0]), [b1] "=&v"(b[1]), [c0] "=&v"(c[0]), [c1] "=&v"(c[1])
-            : [t0x] "v"(g[0].x), [t0y] "v"(g[0].y), [t1x] "v"(g[1].x), [t1y] "v"(g[1].y), [t2x] "v"(g[2].x), [t2y] "v"(g[2].y), [t3x] "v"(g[3].x), [t3y] "v"(g[3].y), [x0] "v"(DX[0]), [y0] "v"(DY[0]), [x1] "v"(DX[1]), [y1] "v"(DY[1]), [cc] "s"(MH_KEY_C), [i0] "s"(ib), [i1] "s"(ib + 1)
-            : "memory");
-    }
-    else if constexpr (NI == 1) {
-        asm volatile(
-            "v_mul_f32_e32 %[a0], %[t0x], %[x0]\n\t"
-            "v_mul_f32_e32 %[b0], %[t0y], %[y0]\n\t"
-            "v_mul_f32_e32 %[c0], %[t2x], %[x0]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_mul_f32_e32 %[b0], %[t2y], %[y0]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_min3_u32 %[e0], %[e0], %[a0], %[c0]\n\t"
-            "v_mul_f32_e32 %[a0], %[t1x], %[x0]\n\t"
-            "v_mul_f32_e32 %[b0], %[t1y], %[y0]\n\t"
-            "v_mul_f32_e32 %[c0], %[t3x], %[x0]\n\t"
-            "v_add_f32_e32 %[a0], %[a0], %[b0]\n\t"
-            "v_mul_f32_e32 %[b0], %[t3y], %[y0]\n\t"
-            "v_sub_f32_e64 %[a0], %[cc], |%[a0]|\n\t"
-            "v_add_f32_e32 %[c0], %[c0], %[b0]\n\t"
-            "v_lshl_or_b32 %[a0], %[a0], 5, %[i0]\n\t"
-            "v_sub_f32_e64 %[c0], %[cc], |%[c0]|\n\t"
-            "v_lshl_or_b32 %[c0], %[c0], 5, %[i1]\n\t"
-            "v_min3_u32 %[o0], %[o0], %[a0], %[c0]"
-            : [e0] "+v"(ke[0]), [o0] "+v"(ko[0]), [a0] "=&v"(a[0]), [b0] "=&v"(b[0]), [c0] "=&v"(c[0])
-            : [t0x] "v"(g[0].x), [t0y] "v"(g[0].y), [t1x] "v"(g[1].x), [t1y] "v"(g[1].y), [t2x] "v"(g[2].x), [t2y] "v"(g[2].y), [t3x] "v"(g[3].x), [t3y] "v"(g[3].y), [x0] "v"(DX[0]), [y0] "v"(DY[0]), [cc] "s"(MH_KEY_C), [i0] "s"(ib), [i1] "s"(ib + 1)
-            : "memory");
-    }
-}
+#include "mh_key_blocks.h"
 
 // ---------------------------------------------------------------------------------------------
 // mh_search3_kernel -- the shipped search: the arithmetic of mh_search_kernel in the same order, laid out for the machine.
@@ -1326,306 +926,6 @@ __global__ __launch_bounds__(1024) void mh_search_order_kernel(int N, int32_t *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// PMVO.refine's loss of ONE given direction per point (PMVO.py:86-90): next = p + dir*mul/div,
-// compute_reproject_ori + compute_prj_loss with S = 1 (then `low_conf_index` is always true and the raw
-// num/den is returned, PMVO.py:199-204).  One wave per point, lane = view; the per-view terms go through
-// LDS so that lane 0 can add them in ATen's cascade order.  Patches are read raw ([V,N,P,..] layout).
-// ---------------------------------------------------------------------------------------------
-#define MH_REFINE_VMAX 512
-__global__ __launch_bounds__(256) void mh_refine_loss_kernel(MhViews vw, const float *__restrict__ pts,
-                                                             const float *__restrict__ dir, float mul, float dv,
-                                                             int N, int P, float thr, const float *__restrict__ vis,
-                                                             const float *__restrict__ ori_patch,
-                                                             const float *__restrict__ conf_patch,
-                                                             float *__restrict__ loss, uint8_t *__restrict__ hcout,
-                                                             MhBatch bt) {
-    __shared__ float s_num[4][MH_REFINE_VMAX], s_den[4][MH_REFINE_VMAX];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + wave;
-    if (n >= N) return;
-    const int V = vw.V;
-    const float Hf = (float)vw.H, Wf = (float)vw.W;
-    const float P0 = pts[3 * n], P1 = pts[3 * n + 1], P2 = pts[3 * n + 2];
-    const float Q0 = P0 + dir[3 * n] * mul / dv, Q1 = P1 + dir[3 * n + 1] * mul / dv,
-                Q2 = P2 + dir[3 * n + 2] * mul / dv;
-    // a batch of ONE point: its [V,1] sums over the views are ATen's inner sums whenever the outer-sum rule is on (sum_block > 0)
-    // and -- with the batch rule of the products (reproject_rule 0) -- its projections are single-column products
-    const bool one_point = mh_batch_single(bt, n);
-    const bool single = bt.single_ok && one_point;
-    for (int v = lane; v < V; v += MH_WAVE) {
-        const float *cam = vw.cams + v * MH_CAM_STRIDE;
-        float r0, c0, r1, c1, dx, dy;
-        mh_pixel_of_b(cam, P0, P1, P2, Hf, Wf, r0, c0, single);
-        mh_pixel_of_b(cam, Q0, Q1, Q2, Hf, Wf, r1, c1, single);
-        mh_unit2(r1 - r0, c1 - c0, dx, dy);
-        const size_t vn = (size_t)v * N + n;
-        const float *__restrict__ cp = conf_patch + vn * P;
-        const float2 *__restrict__ op = reinterpret_cast<const float2 *>(ori_patch) + vn * P;
-        float cmax = cp[0];
-        for (int p = 1; p < P; ++p) cmax = (cp[p] > cmax) ? cp[p] : cmax;
-        const bool hc = cmax > thr;
-        float ml = 0.f, bc = 0.f;
-        for (int p = 0; p < P; ++p) {
-            float o0, o1;
-            const float2 o = op[p];
-            mh_unit2(o.x, o.y, o0, o1);
-            const float cs = o0 * dx + o1 * dy;
-            const float l = 1.0f - __builtin_fabsf(cs);
-            const float c = cp[p];
-            const bool upd = (p == 0) || ((l < ml) && (hc ? (c > thr) : true));
-            ml = upd ? l : ml;
-            bc = upd ? c : bc;
-        }
-        const float w = (vis[vn] == -1.0f ? 0.0f : 1.0f) * bc;
-        s_num[wave][v] = ml * w;
-        s_den[wave][v] = w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        MhCascV nm = {0.f, 0.f, 0.f}, dn = {0.f, 0.f, 0.f};
-        int cnt = 0;
-        for (int v = 0; v < V; ++v) {
-            if (v > 0 && (v & 15) == 0) {
-                mh_cascv_flush(nm, v);
-                mh_cascv_flush(dn, v);
-            }
-            const float w = s_den[wave][v];
-            nm.a0 = nm.a0 + s_num[wave][v];
-            dn.a0 = dn.a0 + w;
-            cnt += (w > 0.0f) ? 1 : 0;
-        }
-        float d = mh_cascv_done(dn), m = mh_cascv_done(nm);
-        if (one_point && bt.block > 0) {   // [V, 1]: ATen's sum over a contiguous innermost dimension
-            m = mh_inner_sum_views(V, [&](int v) { return s_num[wave][v]; });
-            d = mh_inner_sum_views(V, [&](int v) { return s_den[wave][v]; });
-        } else if (mh_tail_row(bt, n)) {   // a trailing column of the batch's [V, N] sums (ATen's row_sum order)
-            m = mh_row_sum_views(V, [&](int v) { return s_num[wave][v]; });
-            d = mh_row_sum_views(V, [&](int v) { return s_den[wave][v]; });
-        }
-        loss[n] = m / d;
-        if (hcout) hcout[n] = (d / (float)cnt > thr) ? 1 : 0;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same loss straight from the maps (refine's smoothing loop, PMVO.py:602-650, calls PMVO.refine once per 5000-point
-// chunk): projection, visibility and the patch of every view that sees the point are evaluated in the kernel, the
-// [V,N,P,..] patch tensors (365 MB per chunk at the headline size) are never written.  Per (view, point) the
-// operations are those of mh_project_gather_kernel followed by mh_refine_loss_kernel, in the same order, so the
-// result is bit-identical to the two-kernel path; views that do not see the point have weight 0 (PMVO.py:212) and
-// are skipped, as in mh_search_kernel.
-// ---------------------------------------------------------------------------------------------
-// Round 6: lane = TAP for the patches.  A wave owns one point.  Phase 1 (lane = view, 64 views at a time): projection,
-// depth test, the projected direction of the candidate.  Phase 2: the views that see the point are walked on the ballot
-// mask; for each, the wave's lanes gather the P taps of the patch as PATCH contiguous runs (one coalesced request per view
-// instead of 2 P per-lane gathers with one address per view -- the round-1..5 form spent 5.1 ms per 288 k points, 4 % of
-// HBM), evaluate 1 - |cos| one tap per lane, and find (a) the patch maximum of the confidence and (b) the lexicographic
-// minimum of (loss, tap index) over tap 0 and the eligible taps with two shuffle reductions.  That IS the sequential rule
-// of compute_prj_loss (PMVO.py:160-190: tap 0 unconditionally, a later tap only if strictly smaller and eligible), NaN
-// cases included: a NaN loss never wins a `<`; a NaN at tap 0 stays.  The next view's taps are requested before the
-// current view is reduced.  Per-view terms go to LDS and lane 0 adds them in ATen's order, as before.
-template <int PATCH>
-__global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, const float *__restrict__ pts,
-                                                                  const float *__restrict__ dir, float mul, float dv,
-                                                                  int N, float thr, float *__restrict__ loss,
-                                                                  uint8_t *__restrict__ hcout, MhBatch bt) {
-    constexpr int P = PATCH * PATCH, HP = PATCH / 2, ROUNDS = (P + MH_WAVE - 1) / MH_WAVE;
-    __shared__ float s_num[4][MH_REFINE_VMAX], s_den[4][MH_REFINE_VMAX];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + wave;
-    if (n >= N) return;
-    const int V = vw.V, H = vw.H, W = vw.W;
-    const float Hf = (float)H, Wf = (float)W;
-    const float P0 = pts[3 * n], P1 = pts[3 * n + 1], P2 = pts[3 * n + 2];
-    const float Q0 = P0 + dir[3 * n] * mul / dv, Q1 = P1 + dir[3 * n + 1] * mul / dv,
-                Q2 = P2 + dir[3 * n + 2] * mul / dv;
-    // a batch of ONE point: its [V,1] sums over the views are ATen's inner sums whenever the outer-sum rule is on (sum_block > 0)
-    // and -- with the batch rule of the products (reproject_rule 0) -- its projections are single-column products
-    const bool one_point = mh_batch_single(bt, n);
-    const bool single = bt.single_ok && one_point;
-    int ti[ROUNDS], tj[ROUNDS];
-#pragma unroll
-    for (int t = 0; t < ROUNDS; ++t) {
-        const int p = min(lane + MH_WAVE * t, P - 1);
-        ti[t] = p / PATCH - HP;
-        tj[t] = p - (p / PATCH) * PATCH - HP;
-    }
-    auto rdf = [](float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); };
-    for (int v0 = 0; v0 < V; v0 += MH_WAVE) {
-        const int v = v0 + lane;
-        float visv = -1.0f, dx = 0.0f, dy = 0.0f;
-        int r = 0, c = 0;
-        if (v < V) {
-            const float *cam = vw.cams + v * MH_CAM_STRIDE;
-            float u, w, z, r0, c0;
-            mh_cam_project_b(cam, P0, P1, P2, u, w, z, single);
-            mh_ndc_to_pixel(u, w, Hf, Wf, r0, c0);
-            float cr = __builtin_rintf(c0), rr = __builtin_rintf(r0);
-            const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-            cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-            rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-            r = (int)rr;
-            c = (int)cr;
-            const float4 q = vw.rec[(size_t)v * H * W + (size_t)r * W + c];
-            visv = oob ? -1.0f : mh_soft_visible(q.w, (-z / 2.0f) * 255.0f);
-            if (visv != -1.0f) {
-                float r1, c1;
-                mh_pixel_of_b(cam, Q0, Q1, Q2, Hf, Wf, r1, c1, single);
-                mh_unit2(r1 - r0, c1 - c0, dx, dy);
-            } else {
-                s_num[wave][v] = 0.0f;
-                s_den[wave][v] = 0.0f;
-            }
-        }
-        unsigned long long m = __ballot(visv != -1.0f);
-        // taps of one view: {unit ori_row, unit ori_col, clamped conf} per lane and round
-        float o0[ROUNDS], o1[ROUNDS], cf[ROUNDS], no0[ROUNDS], no1[ROUNDS], ncf[ROUNDS];
-        auto gather = [&](int src, float *a0, float *a1, float *ac) {
-            const int rv = __builtin_amdgcn_readlane(r, src), cv = __builtin_amdgcn_readlane(c, src);
-            const size_t base = (size_t)(v0 + src) * H * W;
-#pragma unroll
-            for (int t = 0; t < ROUNDS; ++t) {
-                const int r2 = min(max(rv + ti[t], 0), H - 1), c2 = min(max(cv + tj[t], 0), W - 1);
-                if (vw.tap) {   // (the plane of ready-made taps, MhViews::tap: the same values, made once at upload)
-                    const float4 tq = vw.tap[base + (size_t)r2 * W + c2];
-                    a0[t] = tq.x;
-                    a1[t] = tq.y;
-                    ac[t] = tq.z;
-                } else {
-                    const float4 tq = vw.rec[base + (size_t)r2 * W + c2];
-                    mh_unit2(tq.x, tq.y, a0[t], a1[t]);
-                    ac[t] = mh_clampf(tq.z, 1e-6f, 1.0f);
-                }
-            }
-        };
-        int src = m ? __builtin_amdgcn_readfirstlane(__builtin_ctzll(m)) : 0;
-        if (m) gather(src, no0, no1, ncf);
-        while (m) {
-            const int cur = src;
-            m &= m - 1;
-#pragma unroll
-            for (int t = 0; t < ROUNDS; ++t) {
-                o0[t] = no0[t];
-                o1[t] = no1[t];
-                cf[t] = ncf[t];
-            }
-            if (m) {
-                src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
-                gather(src, no0, no1, ncf);
-            }
-            const float dxv = rdf(dx, cur), dyv = rdf(dy, cur);
-            // (a) cmax as `cmax = (p == 0 || cf > cmax) ? cf : cmax` leaves it: the maximum, NaNs skipped -- unless tap 0 is NaN
-            const float cf0 = rdf(cf[0], 0);
-            float mx = -__builtin_inff();
-#pragma unroll
-            for (int t = 0; t < ROUNDS; ++t)
-                if (lane + MH_WAVE * t < P && cf[t] == cf[t]) mx = fmaxf(mx, cf[t]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-            const float cmax = (cf0 != cf0) ? cf0 : mx;
-            const bool hc = cmax > thr;
-            // (b) lexicographic minimum of (loss, tap) over tap 0 and the eligible taps
-            float bl = __builtin_inff(), bcf = 0.0f;
-            int bp = 0x7fffffff;
-            float l0 = 0.0f;
-#pragma unroll
-            for (int t = 0; t < ROUNDS; ++t) {
-                const int p = lane + MH_WAVE * t;
-                const float cs = o0[t] * dxv + o1[t] * dyv;
-                const float l = 1.0f - __builtin_fabsf(cs);
-                if (t == 0) l0 = l;
-                const bool cand = p < P && (p == 0 || ((hc ? (cf[t] > thr) : true) && l == l));
-                if (cand && (bp == 0x7fffffff || l < bl)) {   // (rounds ascend in p: a tie keeps the earlier tap)
-                    bl = l;
-                    bp = p;
-                    bcf = cf[t];
-                }
-            }
-            l0 = rdf(l0, 0);
-            const float c0v = cf0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ol = __shfl_xor(bl, o), oc = __shfl_xor(bcf, o);
-                const int op = __shfl_xor(bp, o);
-                const bool take = op != 0x7fffffff && (bp == 0x7fffffff || ol < bl || (ol == bl && op < bp));
-                bl = take ? ol : bl;
-                bcf = take ? oc : bcf;
-                bp = take ? op : bp;
-            }
-            // a NaN at tap 0 is never replaced (`l < NaN` is false for every later tap)
-            const float ml = (l0 != l0) ? l0 : bl, bc = (l0 != l0) ? c0v : bcf;
-            if (lane == 0) {
-                s_num[wave][v0 + cur] = ml * bc;
-                s_den[wave][v0 + cur] = bc;
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        MhCascV nm = {0.f, 0.f, 0.f}, dn = {0.f, 0.f, 0.f};
-        int cnt = 0;
-        for (int v = 0; v < V; ++v) {
-            if (v > 0 && (v & 15) == 0) {
-                mh_cascv_flush(nm, v);
-                mh_cascv_flush(dn, v);
-            }
-            const float w = s_den[wave][v];
-            nm.a0 = nm.a0 + s_num[wave][v];
-            dn.a0 = dn.a0 + w;
-            cnt += (w > 0.0f) ? 1 : 0;
-        }
-        float d = mh_cascv_done(dn), m = mh_cascv_done(nm);
-        if (one_point && bt.block > 0) {   // [V, 1]: ATen's sum over a contiguous innermost dimension
-            m = mh_inner_sum_views(V, [&](int v) { return s_num[wave][v]; });
-            d = mh_inner_sum_views(V, [&](int v) { return s_den[wave][v]; });
-        } else if (mh_tail_row(bt, n)) {   // a trailing column of the batch's [V, N] sums (ATen's row_sum order)
-            m = mh_row_sum_views(V, [&](int v) { return s_num[wave][v]; });
-            d = mh_row_sum_views(V, [&](int v) { return s_den[wave][v]; });
-        }
-        loss[n] = m / d;
-        if (hcout) hcout[n] = (d / (float)cnt > thr) ? 1 : 0;
-    }
-}
-
-// loss[n] <- -1 where the head filter fires (PMVO.py:91-92), the replacement rule of the smoothing loop on the
-// orientations in place (:631-636, as mh_replace_dissimilar_kernel), and loss -1 -> 0.5 (:641-642) into loss_out
-__global__ __launch_bounds__(256) void mh_refine_combine_kernel(const float *__restrict__ center,
-                                                                const float *__restrict__ loss_u,
-                                                                const uint8_t *__restrict__ head,
-                                                                const uint8_t *__restrict__ head_top, float thr,
-                                                                float *__restrict__ ori, float *__restrict__ loss_out,
-                                                                int N) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const bool filt = head[n] && !head_top[n];
-    const float ul = filt ? -1.0f : loss_u[n];
-    loss_out[n] = (ul == -1.0f) ? 0.5f : ul;
-    if (!ori) return;   // (the replacement was applied already: mh_replace_dissimilar in the chain of the smoothing loop)
-    float c[3], o[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        c[k] = center[3 * n + k];
-        o[k] = ori[3 * n + k];
-    }
-    float sc = c[0] * c[0];
-    sc = mh_fma(c[1], c[1], sc);
-    sc = mh_fma(c[2], c[2], sc);
-    float so = o[0] * o[0];
-    so = mh_fma(o[1], o[1], so);
-    so = mh_fma(o[2], o[2], so);
-    float nc = __builtin_sqrtf(sc), no = __builtin_sqrtf(so);
-    nc = (nc < 1e-8f) ? 1e-8f : nc;
-    no = (no < 1e-8f) ? 1e-8f : no;
-    const float cs = ((c[0] / nc) * (o[0] / no) + (c[1] / nc) * (o[1] / no)) + (c[2] / nc) * (o[2] / no);
-    if (__builtin_fabsf(cs) < thr) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ori[3 * n + k] = c[k];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank, int rank_step, const float *pts,
                                 int N, int P1, float thr, const float *ori_c, const int32_t *base_idx,
                                 const float *base_val, const float4 *taps, int32_t *order /* 2N ints of work space */,
@@ -1689,48 +989,6 @@ extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank,
                            thr, ori_c, base_idx, base_val, taps, line_ori, min_loss, high_conf, best_sample, best_rank,
                            best_s, rule);
     }
-    return (int)hipGetLastError();
-}
-
-extern "C" int mh_launch_refine_loss_maps(MhViews vw, const float *pts, const float *dir, float mul, float dv, int N,
-                                         int patch, float thr, float *loss, uint8_t *hc, int batch, long long row0,
-                                         long long total, int sum_block, hipStream_t st) {
-    if (vw.V > MH_REFINE_VMAX) return -1;
-    const MhBatch bt = {row0, total, batch, sum_block, vw.batch_rule};
-    const dim3 grid((N + 3) / 4), block(256);
-#define MH_RM_CASE(PS)                                                                                               \
-    case PS:                                                                                                         \
-        hipLaunchKernelGGL(mh_refine_loss_maps_kernel<PS>, grid, block, 0, st, vw, pts, dir, mul, dv, N, thr, loss, hc, bt); \
-        break;
-    switch (patch) {
-        MH_RM_CASE(1)
-        MH_RM_CASE(3)
-        MH_RM_CASE(5)
-        MH_RM_CASE(7)
-        MH_RM_CASE(9)
-        MH_RM_CASE(11)
-        default:
-            return -1;
-    }
-#undef MH_RM_CASE
-    return (int)hipGetLastError();
-}
-
-extern "C" int mh_launch_refine_combine(const float *center, const float *loss_u, const uint8_t *head,
-                                        const uint8_t *head_top, float thr, float *ori, float *loss_out, int N,
-                                        hipStream_t st) {
-    hipLaunchKernelGGL(mh_refine_combine_kernel, dim3((N + 255) / 256), dim3(256), 0, st, center, loss_u, head,
-                       head_top, thr, ori, loss_out, N);
-    return (int)hipGetLastError();
-}
-
-extern "C" int mh_launch_refine_loss(MhViews vw, const float *pts, const float *dir, float mul, float dv, int N,
-                                     int P, float thr, const float *vis, const float *ori_patch,
-                                     const float *conf_patch, float *loss, uint8_t *hc, int sum_block, hipStream_t st) {
-    if (vw.V > MH_REFINE_VMAX) return -1;
-    const MhBatch bt = {0, N, 0, sum_block, vw.batch_rule};   // (the stand-alone method: its N points are one batch of the reference)
-    hipLaunchKernelGGL(mh_refine_loss_kernel, dim3((N + 3) / 4), dim3(256), 0, st, vw, pts, dir, mul, dv, N, P, thr,
-                       vis, ori_patch, conf_patch, loss, hc, bt);
     return (int)hipGetLastError();
 }
 

@@ -536,3 +536,17 @@ def test_reference_host_option_is_applied_from_file_and_inline(tmp_path):
     r2 = Rec()
     drv.apply_reference_host(r2, str(f))
     assert ("reproject_fma_min_cols", 2 ** 31 - 1) in r2.calls
+
+
+def test_key_blocks_header_is_the_generator_output():
+    """monohair_amd/csrc/mh_key_blocks.h (the inline-asm blocks of the search's key body) is exactly what
+    tools/gen_key_blocks.py writes."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("gen_key_blocks", os.path.join(ROOT, "tools", "gen_key_blocks.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = gen.header()
+    assert want.endswith("}\n") and all(gen.emit(n) in want for n in (4, 3, 2, 1))
+    with open(os.path.join(ROOT, "monohair_amd", "csrc", "mh_key_blocks.h")) as f:
+        assert f.read() == want
