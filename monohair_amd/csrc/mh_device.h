@@ -44,6 +44,20 @@ __device__ __forceinline__ void mh_ndc_to_pixel(float u, float v, float Hf, floa
     row = ((v + 1.0f) / 2.0f) * Hf;
 }
 
+// PMVO.project_points' round, out_index and clamp of one centre pixel (PMVO.py:383-390): torch.round (half to even), the cast to
+// long, the bounds tests and the clamp on the integers.  The cast is x86's conversion, which the reference leans on: NaN, +-inf
+// and every |x| >= 2^63 become INT64_MIN -- negative, so the pair is out of bounds and its centre clamps to row / column 0
+// (tests/golden/pmvo_border.npz records it).  Returns out_index; r, c = the clamped centre.
+__device__ __forceinline__ bool mh_round_clamp_pixel(float rowf, float colf, int H, int W, int &r, int &c) {
+    float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
+    cr = (__builtin_fabsf(cr) < 9223372036854775808.0f) ? cr : -1.0f;
+    rr = (__builtin_fabsf(rr) < 9223372036854775808.0f) ? rr : -1.0f;
+    const bool oob = (cr > (float)(W - 1)) || (cr < 0.0f) || (rr > (float)(H - 1)) || (rr < 0.0f);
+    c = (int)fminf(fmaxf(cr, 0.0f), (float)(W - 1));
+    r = (int)fminf(fmaxf(rr, 0.0f), (float)(H - 1));
+    return oob;
+}
+
 __device__ __forceinline__ void mh_pixel_of(const float *__restrict__ cam, float X0, float X1, float X2, float Hf,
                                             float Wf, float &row, float &col) {
     float u, v, z;

@@ -140,6 +140,23 @@ __device__ __forceinline__ void mh_tail_item_sums(const float *__restrict__ cams
     cnt_out = cnt;
 }
 
+// A view that does not see the point still enters the reference's sums over views, as loss x weight 0 (PMVO.py:191-198).  Where
+// the point's own pixel position in such a view is not finite (the point lies in that camera's plane, or is not finite itself)
+// D = pix(sample) - pix(point) is NaN for every sample, NaN x 0 = NaN, and every loss of the point is NaN.  The searches skip
+// the views that do not see the point, so they ask here, once per point, whether there is such a view (a view with a non-finite
+// position never sees the point: out_index).  Uniform over the workgroup; holds a barrier.  Pinned by pmvo_border.npz.
+__device__ __forceinline__ bool mh_point_pixel_not_finite(const MhViews &vw, float P0, float P1, float P2, int N, int tid,
+                                                          int T) {
+    const bool single = vw.batch_rule && N == 1;
+    bool bad = false;
+    for (int v = tid; v < vw.V; v += T) {
+        float row, col;
+        mh_pixel_of_b(vw.cams + v * MH_CAM_STRIDE, P0, P1, P2, (float)vw.H, (float)vw.W, row, col, single);
+        bad |= !(__builtin_fabsf(row) < __builtin_inff()) || !(__builtin_fabsf(col) < __builtin_inff());
+    }
+    return __syncthreads_or(bad ? 1 : 0) != 0;
+}
+
 // torch.min over a row with NaN propagation: NaN beats numbers, first index wins among equals
 __device__ __forceinline__ bool mh_min_better(float al, int ai, float bl, int bi) {
     const bool an = al != al, bn = bl != bl;

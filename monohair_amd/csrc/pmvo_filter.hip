@@ -59,11 +59,8 @@ __global__ __launch_bounds__(256) void mh_filter_rows_kernel(MhViews vw, const f
         float u, w, z, rowf, colf;
         mh_cam_project_b(cam, X0, X1, X2, u, w, z, single);
         mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-        const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-        cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-        rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-        const int r = (int)rr, c = (int)cr;
+        int r, c;
+        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
         const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
         const float4 q = rec[(size_t)r * W + c];
         float m = vw.mask[(size_t)v * H * W + (size_t)r * W + c];
@@ -142,11 +139,8 @@ __global__ __launch_bounds__(256) void mh_filter_kernel(MhViews vw, const float 
         float u, w, z, rowf, colf;
         mh_cam_project_b(cam, X0, X1, X2, u, w, z, single);
         mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-        const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-        cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-        rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-        const int r = (int)rr, c = (int)cr;
+        int r, c;
+        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
         const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
         const float4 q = rec[(size_t)r * W + c];
         float m = vw.mask[(size_t)v * H * W + (size_t)r * W + c];

@@ -18,13 +18,11 @@ __global__ __launch_bounds__(256) void mh_project_points_kernel(const float *__r
     float u, w, z, rowf, colf;
     mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, single);
     mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-    float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-    const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-    cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-    rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
+    int r, c;
+    const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
     if (rc) {
-        rc[2 * n] = (int)rr;
-        rc[2 * n + 1] = (int)cr;
+        rc[2 * n] = r;
+        rc[2 * n + 1] = c;
     }
     if (zp) zp[n] = -z / 2.0f;
     if (oobo) oobo[n] = oob ? 1 : 0;

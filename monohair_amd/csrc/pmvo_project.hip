@@ -121,11 +121,8 @@ __global__ __launch_bounds__(256) void mh_project_gather_kernel(MhViews vw, cons
             mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
             mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
             // torch.round (half to even) -> long; bounds tests on the integers (PMVO.py:383-390)
-            float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-            const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-            cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-            rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-            const int r = (int)rr, c = (int)cr;
+            int r, c;
+            const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
             s_r[tid] = r;
             s_c[tid] = c;
             const size_t pix = (size_t)r * W + c;
@@ -425,12 +422,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
         float u, w;
         mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
         mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-        oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-        cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-        rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-        r = (int)rr;
-        c = (int)cr;
+        oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
     }
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f);
     float mk = 0.0f;
@@ -595,12 +587,7 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
         float u, w, z;
         mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
         mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        float cr = __builtin_rintf(colf), rr = __builtin_rintf(rowf);
-        const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-        cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-        rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-        r = (int)rr;
-        c = (int)cr;
+        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
         const float4 q0 = rec[(size_t)r * W + c];
         visv = mh_soft_visible(q0.w, (-z / 2.0f) * 255.0f);
         visv = oob ? -1.0f : visv;

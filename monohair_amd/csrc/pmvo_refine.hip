@@ -140,12 +140,7 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
             float u, w, z, r0, c0;
             mh_cam_project_b(cam, P0, P1, P2, u, w, z, single);
             mh_ndc_to_pixel(u, w, Hf, Wf, r0, c0);
-            float cr = __builtin_rintf(c0), rr = __builtin_rintf(r0);
-            const bool oob = !(cr <= (float)(W - 1)) || (cr < 0.0f) || !(rr <= (float)(H - 1)) || (rr < 0.0f);
-            cr = fminf(fmaxf(cr, 0.0f), (float)(W - 1));
-            rr = fminf(fmaxf(rr, 0.0f), (float)(H - 1));
-            r = (int)rr;
-            c = (int)cr;
+            const bool oob = mh_round_clamp_pixel(r0, c0, H, W, r, c);
             const float4 q = vw.rec[(size_t)v * H * W + (size_t)r * W + c];
             visv = oob ? -1.0f : mh_soft_visible(q.w, (-z / 2.0f) * 255.0f);
             if (visv != -1.0f) {
@@ -153,7 +148,11 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
                 mh_pixel_of_b(cam, Q0, Q1, Q2, Hf, Wf, r1, c1, single);
                 mh_unit2(r1 - r0, c1 - c0, dx, dy);
             } else {
-                s_num[wave][v] = 0.0f;
+                // weight 0, but the reference still adds loss x 0 (PMVO.py:191-198): NaN where this view's D is not finite
+                float r1, c1;
+                mh_pixel_of_b(cam, Q0, Q1, Q2, Hf, Wf, r1, c1, single);
+                mh_unit2(r1 - r0, c1 - c0, dx, dy);
+                s_num[wave][v] = (dx != dx || dy != dy) ? __builtin_nanf("") : 0.0f;
                 s_den[wave][v] = 0.0f;
             }
         }

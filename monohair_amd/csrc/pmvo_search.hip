@@ -143,7 +143,7 @@ __global__ __launch_bounds__(T) void mh_search_kernel(MhViews vw, const float *_
             s_loss[it] = nm / dn;
         }
     }
-    __syncthreads();
+    const bool all_nan = mh_point_pixel_not_finite(vw, P0, P1x, P2, N, tid, T);   // (its barrier covers s_loss / s_pos)
 
     // ---- per rank: low-confidence escape hatch, min / argmin over the S samples (PMVO.py:199-206)
     const int wave = tid >> 6, lane = tid & 63, nwaves = T >> 6;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(T) void mh_search_kernel(MhViews vw, const float *_
         float bl = 0.0f;
         int bi = 0x7fffffff;
         for (int s = lane; s < S; s += MH_WAVE) {
-            float l = s_loss[r * S + s];
+            float l = all_nan ? __builtin_nanf("") : s_loss[r * S + s];
             if (!low && !s_pos[r * S + s]) l = 1.0f;
             if (bi == 0x7fffffff || mh_min_better(l, s, bl, bi)) {
                 bl = l;
@@ -786,6 +786,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
         __syncthreads();
     }
 
+    const bool all_nan = mh_point_pixel_not_finite(vw, P0, P1x, P2, N, tid, T);
     // ---- per rank: low-confidence escape hatch, min / argmin over the S samples (PMVO.py:199-206)
     const int wave = tid >> 6, lane = tid & 63, nwaves = T >> 6;
     for (int r = wave; r < nvalid; r += nwaves) {
@@ -798,7 +799,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
         float bl = 0.0f;
         int bi = 0x7fffffff;
         for (int s = lane; s < S; s += MH_WAVE) {
-            float l = s_loss[r * S + s];
+            float l = all_nan ? __builtin_nanf("") : s_loss[r * S + s];
             if (!low && !s_pos[r * S + s]) l = 1.0f;
             if (bi == 0x7fffffff || mh_min_better(l, s, bl, bi)) {
                 bl = l;

@@ -22,6 +22,7 @@
  * Parity status: PINNED -- checked against golden vectors produced by the imported
  * reference itself (tools/gen_golden.py -> tests/golden/, tests/test_oracle_golden.py).
  */
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -88,8 +89,11 @@ static inline void project_point(const float *cam, const float *X, int H, int W,
     cam_project(cam, X, &u, &v, &z, single);
     ndc_to_pixel(u, v, H, W, &cf, &rf);
     float cr = nearbyintf(cf), rr = nearbyintf(rf);
-    /* torch: round -> long; compare on the integers. NaN/inf never occur for points in front of a camera. */
-    long long ci = (long long)cr, ri = (long long)rr;
+    /* torch: round -> long; compare on the integers.  The cast is x86's conversion, which the reference leans on: NaN, +-inf
+     * and every |x| >= 2^63 become INT64_MIN (negative: out of bounds, clamped to 0) -- written out, a C cast of such a value
+     * is undefined.  Pinned by tests/golden/pmvo_border.npz. */
+    long long ci = fabsf(cr) < 9223372036854775808.0f ? (long long)cr : LLONG_MIN;
+    long long ri = fabsf(rr) < 9223372036854775808.0f ? (long long)rr : LLONG_MIN;
     *oob = (ci > W - 1) || (ci < 0) || (ri > H - 1) || (ri < 0);
     if (ci < 0) ci = 0;
     if (ci > W - 1) ci = W - 1;
