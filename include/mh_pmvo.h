@@ -511,6 +511,59 @@ int mh_strand_match(mh_ctx *ctx, const float *q_points, const double *q_tangents
                     const double *cos_bound, int n_pairs, uint8_t *out_flags, void *stream);
 int mh_flag_counts(mh_ctx *ctx, const uint8_t *flags, const uint8_t *valid, int n, unsigned long long *out9, void *stream);
 
+/* Hair capture (monohair_amd.synth_hair; no counterpart in the reference): a strand set rendered into the four per-view maps
+ * PMVO reads -- depth, orientation code, confidence code, hair mask -- so that a capture exists for which the ground-truth
+ * strands are known.  points [n_points,3] float32 world points, offsets [n_strands+1] (int64, the exclusive scan of the
+ * per-strand point counts).  The rule, per view:
+ *
+ * Vertex.  (u, v, z) = Camera.projection and (row, col) = the unrounded pixel, by the float32 arithmetic PMVO itself projects
+ *   with (mh_project_points: csrc/mh_device.h mh_cam_project, mh_ndc_to_pixel); z255 = (-z / 2) * 255 in float32.  A vertex is
+ *   valid iff z < -0.1 (the camera's near plane) and |row| < 2^20 and |col| < 2^20 (NaN fails).  Everything below is float64
+ *   arithmetic on these float32 values, + - * / sqrt in the order written, nothing fused.
+ * Segment (a, b) = consecutive points of one strand, both valid; any other pair makes nothing.  dr = row_b - row_a, dc = col_b -
+ *   col_a, dz = z255_b - z255_a; n = max(1, ceil(max(|dr|, |dc|))); a segment with n > 8192 is dropped and counted.  len =
+ *   sqrt(dr*dr + dc*dc).  If len > 0: ur = dr/len, uc = dc/len, c2 = uc*uc - ur*ur, s2 = -2*(uc*ur) -- the double angle of the
+ *   line whose (row, col) direction is (-sin phi, cos phi) -- and qc = rint(4096*c2), qs = rint(4096*s2), half to even, as
+ *   integers; otherwise qc = qs = 0.
+ * Sample j = 0 .. n-1: t = (j + 0.5)/n; centre pixel = (rint(row_a + t*dr), rint(col_a + t*dc)), half to even; zf =
+ *   float32(z255_a + t*dz).  A sample whose zf is not finite makes nothing (only |z| beyond 2^121 does that).  Otherwise it
+ *   makes one fragment of depth zf on every pixel of the (2*radius+1)^2 square around the centre that lies inside the image
+ *   (pixels outside are dropped, not clamped).  With an occluder plane depth0 (float32 [H,W], PMVO's depth convention,
+ *   background 255) a fragment with zf > depth0[p] is discarded; equal depth stays.
+ * Pass A: zmin[p] = the smallest zf of the fragments of pixel p, float32 (+inf where there is none).
+ * Pass B: a fragment counts iff zf <= zmin[p] + tol (a float32 addition); per pixel cnt += 1 (int32), C2 += qc, S2 += qs
+ *   (int64).  Integer sums: the result does not depend on the order of arrival.
+ * Resolve, per pixel: mask code 255 if cnt > 0 else 0.  Orientation code: the first k in 0..179 that maximises
+ *   C2*T[k][0] + S2*T[k][1] in float64 (the two products rounded, then their sum), T[k] = the float32 pair (cos 2 theta_k,
+ *   sin 2 theta_k), theta_k = k degrees, widened; 0 where cnt = 0 or C2 = S2 = 0.  Confidence code: min(255, floor((255*coh)*dens
+ *   + 0.5)) with coh = sqrt(C2*C2 + S2*S2) / (4096*cnt) and dens = min(1, cnt / n_full); 0 where cnt = 0.  Depth: zmin[p] where
+ *   cnt > 0, else depth0[p], else 255.
+ * Orientation code k names the line whose (row, col) direction is (-sin theta_k, cos theta_k): the loaders' decode of it
+ * (Utils/PMVO_utils.py:265-272) is parallel to the segment.  Defaults of the callers: radius 1, tol 0.25 (about 2 mm of hair
+ * layer in depth-map units), n_full = 2*radius + 1 (one strand's worth of samples).
+ *
+ * mh_capture_project: vert [n_points,3] = (row, col, z255), valid [n_points].  cam_host: MH_CAM_STRIDE floats (host).
+ * mh_capture_zmin: pass A -> zmin [H,W], dropped (device int32: the segments with n > 8192).  depth0 may be NULL.
+ * mh_capture_accumulate: pass B on the zmin of pass A -> cnt [H,W] int32, c2 / s2 [H,W] int64 (all three are zeroed first).
+ * mh_capture_resolve: table_host = T, 180 x 2 float32 (HOST) -> depth [H,W] float32, ori_u8 / conf_u8 / mask_u8 [H,W].
+ * mh_capture_view: the four steps for one view on a scratch of mh_capture_scratch_bytes(n_points, H, W) bytes: what
+ *   PMVO.from_u8 takes for that view.  0 <= radius <= 16, tol >= 0, n_full >= 1, H*W < 2^31. */
+size_t mh_capture_scratch_bytes(int n_points, int H, int W);
+int mh_capture_project(mh_ctx *ctx, const float *cam_host, const float *points, int n_points, int H, int W, float *vert,
+                       uint8_t *valid, void *stream);
+int mh_capture_zmin(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands,
+                    int n_points, int H, int W, int radius, const float *depth0, float *zmin, int32_t *dropped, void *stream);
+int mh_capture_accumulate(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands,
+                          int n_points, int H, int W, int radius, float tol, const float *depth0, const float *zmin,
+                          int32_t *cnt, long long *c2, long long *s2, void *stream);
+int mh_capture_resolve(mh_ctx *ctx, const float *zmin, const int32_t *cnt, const long long *c2, const long long *s2,
+                       const float *depth0, const float *table_host, int n_full, int H, int W, float *depth, uint8_t *ori_u8,
+                       uint8_t *conf_u8, uint8_t *mask_u8, void *stream);
+int mh_capture_view(mh_ctx *ctx, const float *cam_host, const float *points, const long long *offsets, int n_strands,
+                    int n_points, int H, int W, int radius, float tol, int n_full, const float *depth0,
+                    const float *table_host, void *scratch, size_t scratch_bytes, float *depth, uint8_t *ori_u8,
+                    uint8_t *conf_u8, uint8_t *mask_u8, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

@@ -78,6 +78,12 @@ _SIGS = {
     "mh_strand_tangents": (ci, [vp, vp, vp, ci, ci, vp, vp, vp]),
     "mh_strand_match": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]),
     "mh_flag_counts": (ci, [vp, vp, vp, ci, vp, vp]),
+    "mh_capture_scratch_bytes": (csz, [ci, ci, ci]),
+    "mh_capture_project": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp]),
+    "mh_capture_zmin": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "mh_capture_accumulate": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp]),
+    "mh_capture_resolve": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "mh_capture_view": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, vp, vp, vp, csz, vp, vp, vp, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

@@ -1,6 +1,6 @@
 // capi.cpp -- the C ABI of libmhpmvo.so (include/mh_pmvo.h): argument checking, the context that owns the packed maps, and
 // the launch sequences of the PMVO entry points.  All arithmetic lives in the .hip kernels.  The other stages' entry points
-// are in capi_points.cpp, capi_hair.cpp, capi_image.cpp and capi_comm.cpp; what needs no GPU is in capi_host.cpp.
+// are in capi_points.cpp, capi_hair.cpp, capi_capture.cpp, capi_image.cpp and capi_comm.cpp; what needs no GPU is in capi_host.cpp.
 #include <cstdlib>
 #include <cstring>
 #include <new>

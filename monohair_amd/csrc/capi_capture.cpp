@@ -1,0 +1,100 @@
+// capi_capture.cpp -- C ABI of the hair capture (csrc/haircapture.hip; no counterpart in the reference)
+#include <cstring>
+
+#include "mh_capi.h"
+
+#define MH_CAP_MAX_RADIUS 16
+
+static size_t cap_align(size_t b) { return (b + 255) / 256 * 256; }
+
+static bool cap_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+
+// scratch of mh_capture_view: dropped 256 B | vert | valid | zmin | cnt | c2 | s2
+extern "C" size_t mh_capture_scratch_bytes(int n_points, int H, int W) {
+    if (n_points < 0 || !cap_image_ok(H, W)) return 0;
+    const size_t n = (size_t)(n_points > 0 ? n_points : 1), npix = (size_t)H * W;
+    return 256 + cap_align(n * 12) + cap_align(n) + 2 * cap_align(npix * 4) + 2 * cap_align(npix * 8);
+}
+
+extern "C" int mh_capture_project(mh_ctx *ctx, const float *cam_host, const float *points, int n_points, int H, int W,
+                                  float *vert, uint8_t *valid, void *stream) {
+    if (n_points == 0) return MH_OK;
+    if (!ctx || !cam_host || !points || !vert || !valid || n_points < 0 || !cap_image_ok(H, W))
+        return fail(MH_ERR_ARG, "mh_capture_project: bad arguments");
+    MhCapCam cam;
+    memcpy(cam.c, cam_host, sizeof(cam.c));
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_capture_project(cam, points, n_points, H, W, vert, valid, (hipStream_t)stream),
+                    "mh_capture_project");
+}
+
+static bool cap_strands_ok(const float *vert, const uint8_t *valid, const long long *offsets, int n_strands, int n_points) {
+    return n_strands >= 0 && n_points >= 0 && (n_points == 0 || (vert && valid && offsets && n_strands >= 1));
+}
+
+extern "C" int mh_capture_zmin(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands,
+                               int n_points, int H, int W, int radius, const float *depth0, float *zmin, int32_t *dropped,
+                               void *stream) {
+    if (!ctx || !zmin || !dropped || !cap_strands_ok(vert, valid, offsets, n_strands, n_points) || !cap_image_ok(H, W) ||
+        radius < 0 || radius > MH_CAP_MAX_RADIUS)
+        return fail(MH_ERR_ARG, "mh_capture_zmin: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_capture_zmin(vert, valid, (const int64_t *)offsets, n_strands, n_points, H, W, radius, depth0,
+                                           zmin, dropped, (hipStream_t)stream),
+                    "mh_capture_zmin");
+}
+
+extern "C" int mh_capture_accumulate(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets,
+                                     int n_strands, int n_points, int H, int W, int radius, float tol, const float *depth0,
+                                     const float *zmin, int32_t *cnt, long long *c2, long long *s2, void *stream) {
+    if (!ctx || !zmin || !cnt || !c2 || !s2 || !cap_strands_ok(vert, valid, offsets, n_strands, n_points) ||
+        !cap_image_ok(H, W) || radius < 0 || radius > MH_CAP_MAX_RADIUS || !(tol >= 0.0f))
+        return fail(MH_ERR_ARG, "mh_capture_accumulate: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_capture_accum(vert, valid, (const int64_t *)offsets, n_strands, n_points, H, W, radius, tol,
+                                            depth0, zmin, cnt, c2, s2, (hipStream_t)stream),
+                    "mh_capture_accumulate");
+}
+
+extern "C" int mh_capture_resolve(mh_ctx *ctx, const float *zmin, const int32_t *cnt, const long long *c2,
+                                  const long long *s2, const float *depth0, const float *table_host, int n_full, int H, int W,
+                                  float *depth, uint8_t *ori_u8, uint8_t *conf_u8, uint8_t *mask_u8, void *stream) {
+    if (!ctx || !zmin || !cnt || !c2 || !s2 || !table_host || !depth || !ori_u8 || !conf_u8 || !mask_u8 || n_full < 1 ||
+        !cap_image_ok(H, W))
+        return fail(MH_ERR_ARG, "mh_capture_resolve: bad arguments");
+    MhCapTable tab;
+    memcpy(tab.t, table_host, sizeof(tab.t));
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_capture_resolve(zmin, cnt, c2, s2, depth0, tab, n_full, H, W, depth, ori_u8, conf_u8, mask_u8,
+                                              (hipStream_t)stream),
+                    "mh_capture_resolve");
+}
+
+extern "C" int mh_capture_view(mh_ctx *ctx, const float *cam_host, const float *points, const long long *offsets,
+                               int n_strands, int n_points, int H, int W, int radius, float tol, int n_full,
+                               const float *depth0, const float *table_host, void *scratch, size_t scratch_bytes,
+                               float *depth, uint8_t *ori_u8, uint8_t *conf_u8, uint8_t *mask_u8, void *stream) {
+    if (!ctx || !scratch || n_points < 0 || !cap_image_ok(H, W) || (n_points > 0 && !points))
+        return fail(MH_ERR_ARG, "mh_capture_view: bad arguments");
+    const size_t need = mh_capture_scratch_bytes(n_points, H, W);
+    if (scratch_bytes < need) return fail(MH_ERR_ARG, "mh_capture_view: scratch too small (%zu < %zu)", scratch_bytes, need);
+    const size_t n = (size_t)(n_points > 0 ? n_points : 1), npix = (size_t)H * W;
+    char *base = (char *)scratch;
+    int32_t *dropped = (int32_t *)base;
+    float *vert = (float *)(base += 256);
+    uint8_t *valid = (uint8_t *)(base += cap_align(n * 12));
+    float *zmin = (float *)(base += cap_align(n));
+    int32_t *cnt = (int32_t *)(base += cap_align(npix * 4));
+    long long *c2 = (long long *)(base += cap_align(npix * 4));
+    long long *s2 = (long long *)(base += cap_align(npix * 8));
+    int rc = mh_capture_project(ctx, cam_host, points, n_points, H, W, vert, valid, stream);
+    if (rc == MH_OK)
+        rc = mh_capture_zmin(ctx, vert, valid, offsets, n_strands, n_points, H, W, radius, depth0, zmin, dropped, stream);
+    if (rc == MH_OK)
+        rc = mh_capture_accumulate(ctx, vert, valid, offsets, n_strands, n_points, H, W, radius, tol, depth0, zmin, cnt, c2,
+                                   s2, stream);
+    if (rc == MH_OK)
+        rc = mh_capture_resolve(ctx, zmin, cnt, c2, s2, depth0, table_host, n_full, H, W, depth, ori_u8, conf_u8, mask_u8,
+                                stream);
+    return rc;
+}

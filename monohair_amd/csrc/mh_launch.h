@@ -38,6 +38,14 @@ struct MhMatchPairs {                 // pair k: squared distance bound and cosi
     int K;
 };
 
+#define MH_CAP_MAXN 8192              // hair capture: a segment of more samples than this is dropped and counted
+struct MhCapCam {                     // one camera record, by value (a kernel argument)
+    float c[MH_CAM_STRIDE];
+};
+struct MhCapTable {                   // float32 (cos 2 theta_k, sin 2 theta_k) of the 180 orientation codes, by value
+    float t[180][2];
+};
+
 struct MhRVert;    // raster.hip: a transformed mesh vertex (16 B)
 struct MhRLVert;   // raster.hip: a transformed strand vertex (32 B)
 
@@ -262,4 +270,16 @@ int mh_launch_strand_match(const float *q_pts, const double *q_tan, const uint8_
                            const float *t_pts, const double *t_tan, const int32_t *cstart, float ox, float oy, float oz,
                            float h, int dx, int dy, int dz, MhMatchPairs pr, uint8_t *out, hipStream_t st);
 int mh_launch_flag_counts(const uint8_t *flags, const uint8_t *valid, int n, unsigned long long *out9, hipStream_t st);
+
+// ---- haircapture.hip (loads with its first launch)
+int mh_launch_capture_project(MhCapCam cam, const float *pts, int n, int H, int W, float *vert, uint8_t *valid,
+                              hipStream_t st);
+int mh_launch_capture_zmin(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points, int H, int W,
+                           int radius, const float *depth0, float *zmin, int32_t *dropped, hipStream_t st);
+int mh_launch_capture_accum(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points, int H, int W,
+                            int radius, float tol, const float *depth0, const float *zmin, int32_t *cnt, long long *C2,
+                            long long *S2, hipStream_t st);
+int mh_launch_capture_resolve(const float *zmin, const int32_t *cnt, const long long *C2, const long long *S2,
+                              const float *depth0, MhCapTable tab, int n_full, int H, int W, float *depth, uint8_t *ori,
+                              uint8_t *conf, uint8_t *mask, hipStream_t st);
 }

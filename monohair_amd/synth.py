@@ -203,6 +203,37 @@ def candidate_points(res=256, seed=0, n_per_voxel=4, sphere_r=SPHERE_R, limit=No
     return sample
 
 
+def sphere_obj(path, radius, n_lat=48, n_lon=96, y_min=None, normals=False):
+    """normals: also write the outward unit normals as `vn` records, referenced by `v//vn` faces -- what a fitted
+    scalp_tsfm.obj carries and HairGrow.py reads (the vertex lines and the triangles stay the same)"""
+    vs, fs = [], []
+    for a in range(n_lat + 1):
+        th = math.pi * a / n_lat
+        for b in range(n_lon):
+            ph = 2 * math.pi * b / n_lon
+            vs.append((radius * math.sin(th) * math.cos(ph), radius * math.cos(th), radius * math.sin(th) * math.sin(ph)))
+    for a in range(n_lat):
+        for b in range(n_lon):
+            p00, p01 = a * n_lon + b, a * n_lon + (b + 1) % n_lon
+            p10, p11 = p00 + n_lon, p01 + n_lon
+            fs.append((p00, p10, p11))
+            fs.append((p00, p11, p01))
+    if y_min is not None:
+        keep = {i for i, v in enumerate(vs) if v[1] >= y_min}
+        fs = [t for t in fs if all(i in keep for i in t)]
+    with open(path, "w") as f:
+        for v in vs:
+            f.write("v %.9f %.9f %.9f\n" % v)
+        if normals:
+            for v in vs:
+                f.write("vn %.9f %.9f %.9f\n" % tuple(c / radius for c in v))
+        for t in fs:
+            if normals:
+                f.write("f %d//%d %d//%d %d//%d\n" % tuple(i + 1 for i in t for _ in range(2)))
+            else:
+                f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
+
+
 def write_case(root, case="synthetic_sphere", V=24, H=480, W=270, seed=0, scale=1.7, rings=1, res=64):
     """Write a complete on-disk capture in the reference's layout (SURVEY.md §8b "files in") so that
     `python PMVO.py --yaml=configs/reconstruct/<case>` runs through the real loaders:
@@ -232,36 +263,6 @@ def write_case(root, case="synthetic_sphere", V=24, H=480, W=270, seed=0, scale=
         Image.fromarray(c8).save(os.path.join(base, "conf", name + ".png"))
         Image.fromarray(np.repeat(m8[..., None], 3, axis=2)).save(os.path.join(base, "hair_mask", name + ".png"))
         Image.fromarray(c8).save(os.path.join(base, "capture_images", name + ".png"))
-
-    def sphere_obj(path, radius, n_lat=48, n_lon=96, y_min=None, normals=False):
-        """normals: also write the outward unit normals as `vn` records, referenced by `v//vn` faces -- what a fitted
-        scalp_tsfm.obj carries and HairGrow.py reads (the vertex lines and the triangles stay the same)"""
-        vs, fs = [], []
-        for a in range(n_lat + 1):
-            th = math.pi * a / n_lat
-            for b in range(n_lon):
-                ph = 2 * math.pi * b / n_lon
-                vs.append((radius * math.sin(th) * math.cos(ph), radius * math.cos(th), radius * math.sin(th) * math.sin(ph)))
-        for a in range(n_lat):
-            for b in range(n_lon):
-                p00, p01 = a * n_lon + b, a * n_lon + (b + 1) % n_lon
-                p10, p11 = p00 + n_lon, p01 + n_lon
-                fs.append((p00, p10, p11))
-                fs.append((p00, p11, p01))
-        if y_min is not None:
-            keep = {i for i, v in enumerate(vs) if v[1] >= y_min}
-            fs = [t for t in fs if all(i in keep for i in t)]
-        with open(path, "w") as f:
-            for v in vs:
-                f.write("v %.9f %.9f %.9f\n" % v)
-            if normals:
-                for v in vs:
-                    f.write("vn %.9f %.9f %.9f\n" % tuple(c / radius for c in v))
-            for t in fs:
-                if normals:
-                    f.write("f %d//%d %d//%d %d//%d\n" % tuple(i + 1 for i in t for _ in range(2)))
-                else:
-                    f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
 
     sphere_obj(os.path.join(base, "ours", "colmap_points.obj"), SPHERE_R, n_lat=4 * res // 8, n_lon=8 * res // 8)
     sphere_obj(os.path.join(base, "ours", "bust_long_tsfm.obj"), 0.09, 24, 48)

@@ -1,0 +1,262 @@
+"""A synthetic capture with known strands: a seeded strand model on the synthetic head of `synth.write_case`, and the GPU
+renderer that turns any strand set -- generated here or read from a `.hair` file -- into the four per-view maps PMVO reads
+(depth, orientation code, confidence code, hair mask), either as device-resident planes for `PMVO.from_u8` or as a complete
+on-disk case in the reference's layout with the ground truth next to it:
+
+    python -m monohair_amd.synth_hair --root data --case synthetic_hair [--hair GT.hair] [--views 24 --size 480x270
+                                      --strands 2000 --seed 0 --radius 1 --tol 0.25]
+    python PMVO.py --yaml=configs/reconstruct/synthetic_hair
+    python HairGrow.py --yaml=configs/reconstruct/synthetic_hair
+    python -m monohair_amd.hairmetrics data/synthetic_hair/output/10-16/refine/connected_strands.hair \
+                                       data/synthetic_hair/gt_strands.hair
+
+The reference has no counterpart.  The capture rule is written out in include/mh_pmvo.h ("Hair capture") and restated in
+numpy by tests/hair_capture_np.py; the kernels are csrc/haircapture.hip.  Hair is sub-pixel thin, so a pixel accumulates the
+doubled-angle directions of all the strand samples near its front layer: where strands cross the confidence drops, as a Gabor
+bank's would.  There is no CPU path for the renderer; the strand model is host code (numpy, libm: the same arrays for the same
+seed on one host, not bit for bit between hosts)."""
+import argparse
+import ctypes
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib, synth
+from .camera import camera_records, cameras_from_list
+from .pmvo_utils import _ctx_for, load_strand, read_obj, write_strand
+
+HEAD_R = 0.10          # the scalp sphere of synth.write_case (scalp_tsfm.obj)
+BUST_R = 0.09          # its bust sphere (bust_long_tsfm.obj)
+CAP_Y_MIN = 0.03       # the scalp cap: the part of the sphere with y >= this
+CLEARANCE = 0.0005     # every point after the root stays at least this far outside the head
+MAX_COLMAP_POINTS = 200000
+
+
+def code_table():
+    """float32 [180,2]: (cos 2 theta_k, sin 2 theta_k), theta_k = k degrees -- the table mh_capture_resolve picks the
+    orientation code from (host libm; handed to the kernel, so the host decides its last bits, not the device)."""
+    th = np.arange(180, dtype=np.float64) * (math.pi / 180.0)
+    return np.stack([np.cos(2.0 * th), np.sin(2.0 * th)], -1).astype(np.float32)
+
+
+def make_hairstyle(n_strands=2000, n_points=64, seed=0, length=(0.10, 0.22), gravity=30.0, wave=(0.0, 0.6),
+                   wave_length=(0.02, 0.05)):
+    """A seeded hairstyle on the synthetic head -> (counts int64 [n_strands], points float32 [n_strands * n_points, 3]).
+
+    Roots are uniform on the scalp cap (radius HEAD_R, y >= CAP_Y_MIN).  A strand leaves along the normal, its direction bends
+    towards -y at `gravity` radians per metre, a per-strand helical wave (amplitude drawn from `wave`, in radians of direction;
+    wave length from `wave_length`, metres) turns it about its own axis, and a point that would enter the head is pushed out to
+    HEAD_R + CLEARANCE: long strands wrap around the head and hang below it, so the scene is non-convex and occludes itself."""
+    n_strands, n_points = int(n_strands), int(n_points)
+    if n_strands < 0 or not 2 <= n_points < 65536:
+        raise ValueError("n_strands >= 0 and 2 <= n_points < 65536 (a .hair file counts points in 16 bits)")
+    rng = np.random.default_rng(seed)
+    y = rng.uniform(CAP_Y_MIN, HEAD_R, n_strands)                # uniform in height = uniform in area on a sphere
+    az = rng.uniform(0.0, 2.0 * math.pi, n_strands)
+    rho = np.sqrt(np.maximum(HEAD_R * HEAD_R - y * y, 0.0))
+    normal = np.stack([rho * np.cos(az), y, rho * np.sin(az)], 1) / HEAD_R
+    total = rng.uniform(length[0], length[1], n_strands)
+    amp = rng.uniform(wave[0], wave[1], n_strands)
+    omega = 2.0 * math.pi / rng.uniform(wave_length[0], wave_length[1], n_strands)
+    phase = rng.uniform(0.0, 2.0 * math.pi, n_strands)
+    ds = total / (n_points - 1)
+    down = np.array([0.0, -1.0, 0.0])
+
+    def unit(v):
+        return v / np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)
+
+    pts = np.empty((n_strands, n_points, 3), np.float64)
+    p = normal * HEAD_R
+    d = normal.copy()
+    pts[:, 0] = p
+    for i in range(1, n_points):
+        s = ds * (i - 1)
+        d = unit(d + down * (gravity * ds)[:, None])
+        # a frame across the smooth direction for the wave
+        e1 = unit(np.cross(d, normal + 1e-3))
+        e2 = np.cross(d, e1)
+        w = (amp * np.cos(omega * s + phase))[:, None] * e1 + (amp * np.sin(omega * s + phase))[:, None] * e2
+        p = p + unit(d + w) * ds[:, None]
+        r = np.linalg.norm(p, axis=1)
+        inside = r < HEAD_R + CLEARANCE
+        p = np.where(inside[:, None], p * ((HEAD_R + CLEARANCE) / np.maximum(r, 1e-12))[:, None], p)
+        # a strand that was pushed out goes on along the surface, not into it
+        n_here = p / np.maximum(np.linalg.norm(p, axis=1, keepdims=True), 1e-12)
+        inward = np.minimum((d * n_here).sum(1), 0.0)
+        d = np.where(inside[:, None], unit(d - inward[:, None] * n_here), d)
+        pts[:, i] = p
+    return np.full(n_strands, n_points, np.int64), pts.reshape(-1, 3).astype(np.float32)
+
+
+def _strands(strands):
+    counts, points = strands
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    points = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+    if (counts < 0).any() or int(counts.sum()) != points.shape[0]:
+        raise ValueError("the strand counts sum to %d, there are %d points" % (int(counts.sum()), points.shape[0]))
+    if points.shape[0] >= 1 << 31:
+        raise ValueError("more than 2^31 - 1 points")
+    offs = np.zeros(counts.shape[0] + 1, np.int64)
+    np.cumsum(counts, out=offs[1:])
+    return counts, offs, points
+
+
+def _hp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device="cuda:0", return_details=False,
+                   n_full=None, pixel_center=0.0):
+    """strands = (counts, points); camera: dict view -> Camera (or [V,48] camera records) -> device tensors (depth float32
+    [V,H,W], ori_u8, conf_u8, mask_u8 uint8 [V,H,W]): what PMVO.from_u8 takes.  bust = (vertices, faces): the occluder, drawn
+    by render.DepthRenderer at the integer pixel positions PMVO rounds to (pixel_center 0).  With return_details a fifth value:
+    per view a dict of the accumulators (vert, valid, zmin, cnt, c2, s2 tensors, dropped int, depth0 or None)."""
+    if not torch.cuda.is_available():
+        raise _lib.MhError("monohair_amd.synth_hair needs a ROCm GPU: the renderer has no CPU fallback")
+    device = torch.device(device)
+    H, W, radius = int(H), int(W), int(radius)
+    n_full = 2 * radius + 1 if n_full is None else int(n_full)
+    counts, offs_h, pts_h = _strands(strands)
+    S, n = int(counts.shape[0]), int(pts_h.shape[0])
+    recs = np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
+    V = recs.shape[0]
+    table = code_table()
+    L, ctx = _lib.lib(), _ctx_for(device)
+    with torch.cuda.device(device):
+        st = _lib.stream_ptr()
+        pts = torch.from_numpy(pts_h).to(device)
+        offs = torch.from_numpy(offs_h).to(device)
+        depth = torch.empty((V, H, W), dtype=torch.float32, device=device)
+        ori, conf, mask = (torch.empty((V, H, W), dtype=torch.uint8, device=device) for _ in range(3))
+        renderer = None
+        if bust is not None:
+            from .render import DepthRenderer
+
+            renderer = DepthRenderer([bust], device)
+        details = []
+        scratch = None
+        if not return_details:
+            need = int(L.mh_capture_scratch_bytes(n, H, W))
+            scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        for v in range(V):
+            d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
+            out = (_lib.ptr(depth[v]), _lib.ptr(ori[v]), _lib.ptr(conf[v]), _lib.ptr(mask[v]))
+            if not return_details:
+                _lib.check(L.mh_capture_view(ctx, _hp(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
+                                             n_full, _lib.ptr(d0), _hp(table), _lib.ptr(scratch), scratch.numel(), *out, st),
+                           "mh_capture_view")
+                continue
+            vert = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+            valid = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+            zmin = torch.empty((H, W), dtype=torch.float32, device=device)
+            cnt = torch.empty((H, W), dtype=torch.int32, device=device)
+            c2, s2 = (torch.empty((H, W), dtype=torch.int64, device=device) for _ in range(2))
+            dropped = torch.empty(1, dtype=torch.int32, device=device)
+            _lib.check(L.mh_capture_project(ctx, _hp(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
+                       "mh_capture_project")
+            _lib.check(L.mh_capture_zmin(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, H, W, radius,
+                                         _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(dropped), st), "mh_capture_zmin")
+            _lib.check(L.mh_capture_accumulate(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, H, W, radius,
+                                               float(tol), _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2),
+                                               _lib.ptr(s2), st), "mh_capture_accumulate")
+            _lib.check(L.mh_capture_resolve(ctx, _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2), _lib.ptr(s2), _lib.ptr(d0),
+                                            _hp(table), n_full, H, W, *out, st), "mh_capture_resolve")
+            details.append(dict(vert=vert[:n], valid=valid[:n], zmin=zmin, cnt=cnt, c2=c2, s2=s2, dropped=int(dropped.item()),
+                                depth0=d0))
+        torch.cuda.current_stream().synchronize()      # (the occluder plane and the scratch are read asynchronously)
+    if return_details:
+        return depth, ori, conf, mask, details
+    return depth, ori, conf, mask
+
+
+def write_geometry(base, strands, cams, seed=0):
+    """The files of a case that need no GPU, under the case directory `base`: ours/cam_params.json, the bust and scalp
+    spheres of synth.write_case (the scalp with `vn` records), ours/colmap_points.obj -- a vertices-only OBJ of the strand
+    points (a seeded subsample beyond MAX_COLMAP_POINTS), which the candidate sampling of PMVO.py reads -- and
+    gt_strands.hair, the ground truth.  -> (counts, points) as written"""
+    counts, _, points = _strands(strands)
+    if counts.size and counts.max() >= 65536:
+        raise ValueError("a strand of %d points: a .hair file counts them in 16 bits" % int(counts.max()))
+    os.makedirs(os.path.join(base, "ours"), exist_ok=True)
+    with open(os.path.join(base, "ours", "cam_params.json"), "w") as f:
+        json.dump({"cam_list": cams}, f)
+    synth.sphere_obj(os.path.join(base, "ours", "bust_long_tsfm.obj"), BUST_R, 24, 48)
+    synth.sphere_obj(os.path.join(base, "ours", "scalp_tsfm.obj"), HEAD_R, 24, 48, y_min=CAP_Y_MIN, normals=True)
+    sub = points
+    if len(sub) > MAX_COLMAP_POINTS:
+        sub = sub[np.sort(np.random.default_rng(seed).choice(len(sub), MAX_COLMAP_POINTS, replace=False))]
+    with open(os.path.join(base, "ours", "colmap_points.obj"), "w") as f:
+        f.write("".join("v %.9f %.9f %.9f\n" % (float(p[0]), float(p[1]), float(p[2])) for p in sub))
+    write_strand(points, os.path.join(base, "gt_strands.hair"), [int(c) for c in counts])
+    return counts, points
+
+
+def write_case(root, case="synthetic_hair", V=24, H=480, W=270, seed=0, n_strands=2000, n_points=64, strands=None, radius=1,
+               tol=0.25, scale=1.7, rings=1, device="cuda:0"):
+    """Write a complete on-disk capture of a strand set in the layout of synth.write_case, so that
+    `python PMVO.py --yaml=configs/reconstruct/<case>` and `python HairGrow.py ...` run on it through the real loaders:
+      the files of write_geometry, capture_images/<view>.png, render_depth/<view>.npy [H,W,3] f32, best_ori/<view>.png (u8
+      degrees), conf/<view>.png (u8), hair_mask/<view>.png.
+    strands = (counts, points) renders that set instead of make_hairstyle(n_strands, n_points, seed).  -> the case directory"""
+    from PIL import Image
+
+    base = os.path.join(root, case)
+    for d in ("ours", "capture_images", "render_depth", "best_ori", "conf", "hair_mask"):
+        os.makedirs(os.path.join(base, d), exist_ok=True)
+    if strands is None:
+        strands = make_hairstyle(n_strands, n_points, seed)
+    cams = synth.make_cameras(V, H, W, scale=scale, rings=rings)
+    counts, points = write_geometry(base, strands, cams, seed)
+    bust = read_obj(os.path.join(base, "ours", "bust_long_tsfm.obj"))
+    depth, ori, conf, mask = capture_planes((counts, points), cameras_from_list(cams), H, W, radius=radius, tol=tol,
+                                            bust=bust, device=device)
+    depth, ori, conf, mask = (t.cpu().numpy() for t in (depth, ori, conf, mask))
+    for i, cam in enumerate(cams):
+        name = cam["file"]
+        np.save(os.path.join(base, "render_depth", name + ".npy"), np.repeat(depth[i][..., None], 3, axis=2))
+        Image.fromarray(ori[i]).save(os.path.join(base, "best_ori", name + ".png"))
+        Image.fromarray(conf[i]).save(os.path.join(base, "conf", name + ".png"))
+        Image.fromarray(np.repeat(mask[i][..., None], 3, axis=2)).save(os.path.join(base, "hair_mask", name + ".png"))
+        Image.fromarray(conf[i]).save(os.path.join(base, "capture_images", name + ".png"))
+    return base
+
+
+def _size(text):
+    h, sep, w = text.lower().partition("x")
+    if not sep:
+        raise argparse.ArgumentTypeError("size %r is not HxW" % text)
+    return int(h), int(w)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m monohair_amd.synth_hair",
+                                 description="write a synthetic capture whose ground-truth strands are known")
+    ap.add_argument("--root", default="data")
+    ap.add_argument("--case", default="synthetic_hair")
+    ap.add_argument("--hair", default=None, help="render this .hair file instead of a generated hairstyle")
+    ap.add_argument("--views", type=int, default=24)
+    ap.add_argument("--size", type=_size, default=(480, 270), help="HxW in pixels (default 480x270)")
+    ap.add_argument("--strands", type=int, default=2000)
+    ap.add_argument("--points", type=int, default=64, help="points per generated strand")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--radius", type=int, default=1)
+    ap.add_argument("--tol", type=float, default=0.25)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    strands = None
+    if args.hair:
+        segments, points = load_strand(args.hair)
+        strands = (np.asarray(segments, np.int64), points.astype(np.float32))
+    base = write_case(args.root, args.case, V=args.views, H=args.size[0], W=args.size[1], seed=args.seed,
+                      n_strands=args.strands, n_points=args.points, strands=strands, radius=args.radius, tol=args.tol,
+                      device=args.device)
+    print("wrote %s (ground truth: %s)" % (base, os.path.join(base, "gt_strands.hair")))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
