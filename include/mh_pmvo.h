@@ -564,6 +564,55 @@ int mh_capture_view(mh_ctx *ctx, const float *cam_host, const float *points, con
                     const float *table_host, void *scratch, size_t scratch_bytes, float *depth, uint8_t *ori_u8,
                     uint8_t *conf_u8, uint8_t *mask_u8, void *stream);
 
+/* Hair photograph (monohair_amd.synth_hair.photo_planes; no counterpart in the reference): the same strand set rendered as
+ * the 8-bit gray images a capture consists of -- thin, shaded, mutually occluding strands, anti-aliased by supersampling -- so
+ * that capture_images/ holds pictures and the Gabor stage (mh_gabor_view) makes best_ori/ and conf/ from them.  Per view there
+ * is a supersampling factor S in {1, 2, 4, 8} and a sub-pixel half-width w, 0 <= w <= 16; S*H * S*W < 2^31.  The rule:
+ *
+ * Vertex.  mh_capture_project unchanged: (row, col, z255, valid).  Everything below is float64 arithmetic on float32 values,
+ *   + - * / sqrt in the order written, nothing fused; every per-pixel quantity is an integer.
+ * Sub-pixel grid.  S*H x S*W sub-pixels; row' = S*row + (S-1)/2, col' = S*col + (S-1)/2.  Sub-pixel (r', c') belongs to pixel
+ *   (r' div S, c' div S): pixel p owns the sub-pixel centres in [p - 1/2, p + 1/2), the positions PMVO rounds to p (but for
+ *   the ties: at S > 1 a sample centred exactly on k + 1/2 goes to pixel k + 1, PMVO's half-to-even rounding gives it to the
+ *   even one of k and k + 1; at S = 1 the two agree everywhere).
+ * Segment (a, b) = consecutive points of one strand, both valid; any other pair makes nothing.  It is walked as the capture
+ *   rule walks it, in sub-pixel units: dr = row'_b - row'_a, dc = col'_b - col'_a, dz = z255_b - z255_a; n = max(1,
+ *   ceil(max(|dr|, |dc|))); a segment with n > 8192 is dropped and counted.  Sample j = 0 .. n-1: t = (j + 0.5)/n; centre
+ *   sub-pixel = (rint(row'_a + t*dr), rint(col'_a + t*dc)), half to even; zf = float32(z255_a + t*dz); a sample whose zf is
+ *   not finite makes nothing.  Otherwise it makes one fragment (zf, q) on every sub-pixel of the (2w+1)^2 square around the
+ *   centre that lies inside the grid.  With an occluder plane depth0 (float32 [H,W], at image resolution) a fragment with
+ *   zf > depth0[owning pixel] is discarded; equal depth stays.
+ * Shade of a segment, one integer q in 0..255 (the Kajiya-Kay diffuse term): T = P_b - P_a from the float32 world points
+ *   widened to float64; tt = (Tx*Tx + Ty*Ty) + Tz*Tz, tl = (Tx*Lx + Ty*Ly) + Tz*Lz; sin = sqrt(max(0, 1 - (tl*tl)/tt)) if
+ *   tt > 0, else 0; v = (255*albedo[s]) * (ambient + (1 - ambient)*sin); q = min(255, rint(v)), half to even, if v > 0, else 0
+ *   (NaN included).  L is a unit 3-vector per view (float64, host; the callers' default is the view's direction towards the
+ *   camera, a head light), albedo a float32 table with one entry per strand (the host decides its bits, as with T above),
+ *   0 <= ambient <= 1.  shade[i] is the q of segment (i, i+1), 0 where the pair makes no segment.
+ * Front pass.  Each sub-pixel holds one unsigned 64-bit key, (bits(zf) << 32) | q; zf > 0 for valid vertices, so the bits
+ *   order as the values do.  The plane starts as all ones and takes the minimum over the fragments: the nearest strand wins,
+ *   and at exactly equal depth the darker shade wins.  An integer minimum: the result does not depend on the order of arrival.
+ * Resolve, per pixel: sum over its S^2 sub-pixels of the key's q where a fragment arrived, else bust_code where depth0 is given
+ *   and depth0[p] < 255, else background_code (both 0..255).  gray = (2*sum + S^2) div (2*S^2) as uint8 (the mean, half up);
+ *   cover = the number of sub-pixels where a fragment arrived, int32.
+ *
+ * mh_photo_shade: valid = mh_capture_project's -> shade [n_points] uint8.  light_host: 3 doubles (HOST).
+ * mh_photo_front: keys [S*H, S*W] (filled first), dropped (device int32: the segments with n > 8192).  depth0 may be NULL.
+ * mh_photo_resolve: gray_u8 [H,W], cover [H,W] int32 (may be NULL).
+ * mh_photo_view: mh_capture_project and the three steps for one view on a scratch of mh_photo_scratch_bytes(n_points, H, W,
+ *   supersample) bytes, whose first int32 is left holding the dropped count. */
+size_t mh_photo_scratch_bytes(int n_points, int H, int W, int supersample);
+int mh_photo_shade(mh_ctx *ctx, const float *points, const uint8_t *valid, const long long *offsets, int n_strands,
+                   int n_points, const float *albedo, const double *light_host, double ambient, uint8_t *shade, void *stream);
+int mh_photo_front(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands, int n_points,
+                   const uint8_t *shade, int H, int W, int supersample, int width, const float *depth0,
+                   unsigned long long *keys, int32_t *dropped, void *stream);
+int mh_photo_resolve(mh_ctx *ctx, const unsigned long long *keys, const float *depth0, int H, int W, int supersample,
+                     int bust_code, int background_code, uint8_t *gray_u8, int32_t *cover, void *stream);
+int mh_photo_view(mh_ctx *ctx, const float *cam_host, const float *points, const long long *offsets, int n_strands,
+                  int n_points, const float *albedo, const double *light_host, double ambient, int H, int W, int supersample,
+                  int width, const float *depth0, int bust_code, int background_code, void *scratch, size_t scratch_bytes,
+                  uint8_t *gray_u8, int32_t *cover, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

@@ -84,6 +84,12 @@ _SIGS = {
     "mh_capture_accumulate": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp]),
     "mh_capture_resolve": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_capture_view": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, vp, vp, vp, csz, vp, vp, vp, vp, vp]),
+    "mh_photo_scratch_bytes": (csz, [ci, ci, ci, ci]),
+    "mh_photo_shade": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, vp, vp]),
+    "mh_photo_front": (ci, [vp, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "mh_photo_resolve": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "mh_photo_view": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, ci, ci, ci, ci, vp, ci, ci, vp, csz, vp, vp,
+                           vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

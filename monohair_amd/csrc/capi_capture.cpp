@@ -98,3 +98,83 @@ extern "C" int mh_capture_view(mh_ctx *ctx, const float *cam_host, const float *
                                 stream);
     return rc;
 }
+
+// ---- the photograph rule
+
+#define MH_PHOTO_MAX_WIDTH 16
+
+static bool photo_grid_ok(int H, int W, int ss) {
+    return H >= 1 && W >= 1 && (ss == 1 || ss == 2 || ss == 4 || ss == 8) && (long long)H * ss * W * ss < (1ll << 31);
+}
+
+static bool photo_code_ok(int code) { return code >= 0 && code <= 255; }
+
+// scratch of mh_photo_view: dropped 256 B | vert | valid | shade | keys
+extern "C" size_t mh_photo_scratch_bytes(int n_points, int H, int W, int supersample) {
+    if (n_points < 0 || !photo_grid_ok(H, W, supersample)) return 0;
+    const size_t n = (size_t)(n_points > 0 ? n_points : 1), nsub = (size_t)H * supersample * W * supersample;
+    return 256 + cap_align(n * 12) + 2 * cap_align(n) + cap_align(nsub * 8);
+}
+
+extern "C" int mh_photo_shade(mh_ctx *ctx, const float *points, const uint8_t *valid, const long long *offsets, int n_strands,
+                              int n_points, const float *albedo, const double *light_host, double ambient, uint8_t *shade,
+                              void *stream) {
+    if (n_points == 0 && n_strands >= 0) return MH_OK;
+    if (!ctx || !points || !valid || !offsets || !albedo || !light_host || !shade || n_strands < 1 || n_points < 0 ||
+        !(ambient >= 0.0 && ambient <= 1.0))
+        return fail(MH_ERR_ARG, "mh_photo_shade: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_photo_shade(points, valid, (const int64_t *)offsets, n_strands, n_points, albedo, light_host[0],
+                                          light_host[1], light_host[2], ambient, shade, (hipStream_t)stream),
+                    "mh_photo_shade");
+}
+
+extern "C" int mh_photo_front(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands,
+                              int n_points, const uint8_t *shade, int H, int W, int supersample, int width,
+                              const float *depth0, unsigned long long *keys, int32_t *dropped, void *stream) {
+    if (!ctx || !keys || !dropped || !cap_strands_ok(vert, valid, offsets, n_strands, n_points) || (n_points > 0 && !shade) ||
+        !photo_grid_ok(H, W, supersample) || width < 0 || width > MH_PHOTO_MAX_WIDTH)
+        return fail(MH_ERR_ARG, "mh_photo_front: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_photo_front(vert, valid, (const int64_t *)offsets, n_strands, n_points, shade, H, W, supersample,
+                                          width, depth0, keys, dropped, (hipStream_t)stream),
+                    "mh_photo_front");
+}
+
+extern "C" int mh_photo_resolve(mh_ctx *ctx, const unsigned long long *keys, const float *depth0, int H, int W,
+                                int supersample, int bust_code, int background_code, uint8_t *gray_u8, int32_t *cover,
+                                void *stream) {
+    if (!ctx || !keys || !gray_u8 || !photo_grid_ok(H, W, supersample) || !photo_code_ok(bust_code) ||
+        !photo_code_ok(background_code))
+        return fail(MH_ERR_ARG, "mh_photo_resolve: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_photo_resolve(keys, depth0, H, W, supersample, bust_code, background_code, gray_u8, cover,
+                                            (hipStream_t)stream),
+                    "mh_photo_resolve");
+}
+
+extern "C" int mh_photo_view(mh_ctx *ctx, const float *cam_host, const float *points, const long long *offsets, int n_strands,
+                             int n_points, const float *albedo, const double *light_host, double ambient, int H, int W,
+                             int supersample, int width, const float *depth0, int bust_code, int background_code,
+                             void *scratch, size_t scratch_bytes, uint8_t *gray_u8, int32_t *cover, void *stream) {
+    if (!ctx || !scratch || n_points < 0 || !photo_grid_ok(H, W, supersample) || (n_points > 0 && !points))
+        return fail(MH_ERR_ARG, "mh_photo_view: bad arguments");
+    const size_t need = mh_photo_scratch_bytes(n_points, H, W, supersample);
+    if (scratch_bytes < need) return fail(MH_ERR_ARG, "mh_photo_view: scratch too small (%zu < %zu)", scratch_bytes, need);
+    const size_t n = (size_t)(n_points > 0 ? n_points : 1);
+    char *base = (char *)scratch;
+    int32_t *dropped = (int32_t *)base;
+    float *vert = (float *)(base += 256);
+    uint8_t *valid = (uint8_t *)(base += cap_align(n * 12));
+    uint8_t *shade = (uint8_t *)(base += cap_align(n));
+    unsigned long long *keys = (unsigned long long *)(base += cap_align(n));
+    int rc = mh_capture_project(ctx, cam_host, points, n_points, H, W, vert, valid, stream);
+    if (rc == MH_OK)
+        rc = mh_photo_shade(ctx, points, valid, offsets, n_strands, n_points, albedo, light_host, ambient, shade, stream);
+    if (rc == MH_OK)
+        rc = mh_photo_front(ctx, vert, valid, offsets, n_strands, n_points, shade, H, W, supersample, width, depth0, keys,
+                            dropped, stream);
+    if (rc == MH_OK)
+        rc = mh_photo_resolve(ctx, keys, depth0, H, W, supersample, bust_code, background_code, gray_u8, cover, stream);
+    return rc;
+}

@@ -11,6 +11,13 @@
 //   mh_capture_pass_kernel<1>   pass B, one lane per segment: cnt / C2 / S2 of the fragments within `tol` of the nearest
 //   mh_capture_resolve_kernel   one lane per pixel: depth, orientation code, confidence code, mask code
 //
+// The photograph rule ("Hair photograph" in the same header, restated by tests/hair_photo_np.py) draws the same strands as
+// 8-bit gray images on an S x S supersampled grid, with the vertex step, the strand lookup and the segment walk above it:
+//   mh_photo_shade_kernel       one lane per segment: the Kajiya-Kay diffuse shade q of the world segment, 0..255
+//   mh_photo_fill_kernel        the key plane set to all ones
+//   mh_photo_front_kernel       one lane per segment: atomicMin of (bits(zf) << 32 | q) on every sub-pixel of its fragments
+//   mh_photo_resolve_kernel     one lane per pixel: the S^2 keys of its sub-pixels -> gray, cover
+//
 // A segment makes n <= MH_CAP_MAXN samples of (2 radius + 1)^2 fragments each: a lane's loop is short (hair segments are a few
 // pixels long) and its atomics go to a few neighbouring lines of the pixel planes.  Fragments outside the image are skipped
 // before any address is formed.
@@ -45,31 +52,45 @@ __global__ __launch_bounds__(256) void mh_capture_project_kernel(MhCapCam cam, c
     valid[i] = (z < -0.1f && __builtin_fabsf(row) < 1048576.0f && __builtin_fabsf(col) < 1048576.0f) ? 1 : 0;
 }
 
-// What both passes need of segment (i, i+1), the same arithmetic in both.
+// What the passes need of segment (i, i+1), the same arithmetic in all of them.
 struct MhCapSeg {
     double r0, c0, z0, dr, dc, dz;
     int n;
     long long qc, qs;
 };
 
+// true: points i and i+1 are consecutive points of one strand and both valid
+__device__ __forceinline__ bool mh_cap_pair(const uint8_t *__restrict__ valid, const int64_t *__restrict__ offs, int S,
+                                            int64_t i) {
+    const int s = mh_cap_strand_of(offs, S, i);
+    return s < S && i + 1 < offs[s + 1] && valid[i] && valid[i + 1];                    // (s = S: i beyond the offsets)
+}
+
+// the walk from (r0, c0, z0) to (r1, c1, z1), in whatever units the caller's grid has: the steps and the sample count.
+// false: the segment is dropped (n > MH_CAP_MAXN)
+__device__ __forceinline__ bool mh_cap_walk(MhCapSeg &sg, double r0, double c0, double z0, double r1, double c1, double z1) {
+    sg.r0 = r0, sg.c0 = c0, sg.z0 = z0;
+    sg.dr = r1 - r0;
+    sg.dc = c1 - c0;
+    sg.dz = z1 - z0;
+    const double m = fmax(fabs(sg.dr), fabs(sg.dc));      // < 2^24: both ends are valid
+    const double nn = fmax(1.0, ceil(m));
+    if (nn > (double)MH_CAP_MAXN) return false;
+    sg.n = (int)nn;
+    return true;
+}
+
 // false: no segment starts at point i (last point of its strand, an invalid end), or it is dropped (n > MH_CAP_MAXN: *too_long)
 __device__ __forceinline__ bool mh_cap_segment(const float *__restrict__ vert, const uint8_t *__restrict__ valid,
                                                const int64_t *__restrict__ offs, int S, int64_t i, MhCapSeg &sg,
                                                bool &too_long) {
     too_long = false;
-    const int s = mh_cap_strand_of(offs, S, i);
-    if (s >= S || i + 1 >= offs[s + 1] || !valid[i] || !valid[i + 1]) return false;      // (s = S: i beyond the offsets)
-    sg.r0 = (double)vert[3 * i], sg.c0 = (double)vert[3 * i + 1], sg.z0 = (double)vert[3 * i + 2];
-    sg.dr = (double)vert[3 * i + 3] - sg.r0;
-    sg.dc = (double)vert[3 * i + 4] - sg.c0;
-    sg.dz = (double)vert[3 * i + 5] - sg.z0;
-    const double m = fmax(fabs(sg.dr), fabs(sg.dc));      // < 2^21: both ends are valid
-    const double nn = fmax(1.0, ceil(m));
-    if (nn > (double)MH_CAP_MAXN) {
+    if (!mh_cap_pair(valid, offs, S, i)) return false;
+    if (!mh_cap_walk(sg, (double)vert[3 * i], (double)vert[3 * i + 1], (double)vert[3 * i + 2], (double)vert[3 * i + 3],
+                     (double)vert[3 * i + 4], (double)vert[3 * i + 5])) {
         too_long = true;
         return false;
     }
-    sg.n = (int)nn;
     const double len = sqrt(sg.dr * sg.dr + sg.dc * sg.dc);
     sg.qc = sg.qs = 0;
     if (len > 0.0) {
@@ -216,5 +237,123 @@ extern "C" int mh_launch_capture_resolve(const float *zmin, const int32_t *cnt, 
     const size_t npix = (size_t)H * W;
     hipLaunchKernelGGL(mh_capture_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, zmin, cnt, C2, S2,
                        depth0, tab, n_full, npix, depth, ori, conf, mask);
+    return (int)hipGetLastError();
+}
+
+// ---- the photograph rule
+
+__global__ __launch_bounds__(256) void mh_photo_shade_kernel(const float *__restrict__ pts, const uint8_t *__restrict__ valid,
+                                                             const int64_t *__restrict__ offs, int S, int n_points,
+                                                             const float *__restrict__ albedo, double lx, double ly, double lz,
+                                                             double ambient, uint8_t *__restrict__ shade) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_points) return;
+    const int s = mh_cap_strand_of(offs, S, i);
+    if (s >= S || i + 1 >= offs[s + 1] || !valid[i] || !valid[i + 1]) {
+        shade[i] = 0;
+        return;
+    }
+    // (both ends valid: the world points are finite)
+    const double tx = (double)pts[3 * i + 3] - (double)pts[3 * i];
+    const double ty = (double)pts[3 * i + 4] - (double)pts[3 * i + 1];
+    const double tz = (double)pts[3 * i + 5] - (double)pts[3 * i + 2];
+    const double tt = (tx * tx + ty * ty) + tz * tz;
+    const double tl = (tx * lx + ty * ly) + tz * lz;
+    double sn = 0.0;
+    if (tt > 0.0) sn = sqrt(fmax(0.0, 1.0 - (tl * tl) / tt));
+    const double v = (255.0 * (double)albedo[s]) * (ambient + (1.0 - ambient) * sn);
+    shade[i] = v > 0.0 ? (uint8_t)(int)fmin(255.0, rint(v)) : 0;      // (NaN fails the comparison)
+}
+
+__global__ __launch_bounds__(256) void mh_photo_fill_kernel(unsigned long long *__restrict__ p, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = ~0ull;
+}
+
+// ss: the supersampling factor; H, W: the image; the key plane is [ss H, ss W]
+__global__ __launch_bounds__(256) void mh_photo_front_kernel(const float *__restrict__ vert, const uint8_t *__restrict__ valid,
+                                                             const int64_t *__restrict__ offs, int S, int n_points,
+                                                             const uint8_t *__restrict__ shade, int H, int W, int ss,
+                                                             int width, const float *__restrict__ depth0,
+                                                             unsigned long long *__restrict__ keys,
+                                                             int32_t *__restrict__ dropped) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i + 1 >= n_points) return;
+    if (!mh_cap_pair(valid, offs, S, i)) return;
+    const double k = (double)ss, h = (double)(ss - 1) / 2.0;
+    MhCapSeg sg;
+    if (!mh_cap_walk(sg, k * (double)vert[3 * i] + h, k * (double)vert[3 * i + 1] + h, (double)vert[3 * i + 2],
+                     k * (double)vert[3 * i + 3] + h, k * (double)vert[3 * i + 4] + h, (double)vert[3 * i + 5])) {
+        atomicAdd(dropped, 1);
+        return;
+    }
+    const unsigned long long q = shade[i];
+    const int HS = H * ss, WS = W * ss;
+    for (int j = 0; j < sg.n; ++j) {
+        int cr, cc;
+        float zf;
+        if (!mh_cap_sample(sg, j, cr, cc, zf)) continue;
+        // (|centre| <= 2^23 + 4: the additions below cannot overflow)
+        const int ra = max(cr - width, 0), rb = min(cr + width, HS - 1);
+        const int ca = max(cc - width, 0), cb = min(cc + width, WS - 1);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(zf) << 32) | q;      // zf > 0
+        for (int r = ra; r <= rb; ++r)
+            for (int c = ca; c <= cb; ++c) {
+                if (depth0 && zf > depth0[(size_t)(r / ss) * W + c / ss]) continue;
+                atomicMin(keys + ((size_t)r * WS + c), key);
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void mh_photo_resolve_kernel(const unsigned long long *__restrict__ keys,
+                                                               const float *__restrict__ depth0, int H, int W, int ss,
+                                                               int bust_code, int background_code,
+                                                               uint8_t *__restrict__ gray, int32_t *__restrict__ cover) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (size_t)H * W) return;
+    const int pr = (int)(p / W), pc = (int)(p % W);
+    const int empty = (depth0 && depth0[p] < 255.0f) ? bust_code : background_code;
+    const size_t WS = (size_t)W * ss;
+    const unsigned long long *row = keys + ((size_t)pr * ss) * WS + (size_t)pc * ss;
+    int sum = 0, hair = 0;
+    for (int a = 0; a < ss; ++a, row += WS)
+        for (int b = 0; b < ss; ++b) {
+            const unsigned long long key = row[b];
+            if (key != ~0ull) sum += (int)(key & 0xffull), ++hair;
+            else sum += empty;
+        }
+    const int s2 = ss * ss;
+    gray[p] = (uint8_t)((2 * sum + s2) / (2 * s2));
+    if (cover) cover[p] = hair;
+}
+
+extern "C" int mh_launch_photo_shade(const float *pts, const uint8_t *valid, const int64_t *offs, int S, int n_points,
+                                     const float *albedo, double lx, double ly, double lz, double ambient, uint8_t *shade,
+                                     hipStream_t st) {
+    if (n_points < 1) return 0;
+    hipLaunchKernelGGL(mh_photo_shade_kernel, dim3((n_points + 255) / 256), dim3(256), 0, st, pts, valid, offs, S, n_points,
+                       albedo, lx, ly, lz, ambient, shade);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mh_launch_photo_front(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points,
+                                     const uint8_t *shade, int H, int W, int ss, int width, const float *depth0,
+                                     unsigned long long *keys, int32_t *dropped, hipStream_t st) {
+    const size_t nsub = (size_t)H * ss * W * ss;
+    hipLaunchKernelGGL(mh_photo_fill_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, keys, nsub);
+    int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    if ((rc = mh_cap_fill(dropped, 0u, 1, st))) return rc;
+    if (n_points < 2) return 0;
+    hipLaunchKernelGGL(mh_photo_front_kernel, dim3((n_points - 1 + 255) / 256), dim3(256), 0, st, vert, valid, offs, S,
+                       n_points, shade, H, W, ss, width, depth0, keys, dropped);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mh_launch_photo_resolve(const unsigned long long *keys, const float *depth0, int H, int W, int ss,
+                                       int bust_code, int background_code, uint8_t *gray, int32_t *cover, hipStream_t st) {
+    const size_t npix = (size_t)H * W;
+    hipLaunchKernelGGL(mh_photo_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, keys, depth0, H, W, ss,
+                       bust_code, background_code, gray, cover);
     return (int)hipGetLastError();
 }

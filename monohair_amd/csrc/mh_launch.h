@@ -282,4 +282,12 @@ int mh_launch_capture_accum(const float *vert, const uint8_t *valid, const int64
 int mh_launch_capture_resolve(const float *zmin, const int32_t *cnt, const long long *C2, const long long *S2,
                               const float *depth0, MhCapTable tab, int n_full, int H, int W, float *depth, uint8_t *ori,
                               uint8_t *conf, uint8_t *mask, hipStream_t st);
+int mh_launch_photo_shade(const float *pts, const uint8_t *valid, const int64_t *offs, int S, int n_points,
+                          const float *albedo, double lx, double ly, double lz, double ambient, uint8_t *shade,
+                          hipStream_t st);
+int mh_launch_photo_front(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points,
+                          const uint8_t *shade, int H, int W, int ss, int width, const float *depth0,
+                          unsigned long long *keys, int32_t *dropped, hipStream_t st);
+int mh_launch_photo_resolve(const unsigned long long *keys, const float *depth0, int H, int W, int ss, int bust_code,
+                            int background_code, uint8_t *gray, int32_t *cover, hipStream_t st);
 }

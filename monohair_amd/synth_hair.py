@@ -5,6 +5,7 @@ on-disk case in the reference's layout with the ground truth next to it:
 
     python -m monohair_amd.synth_hair --root data --case synthetic_hair [--hair GT.hair] [--views 24 --size 480x270
                                       --strands 2000 --seed 0 --radius 1 --tol 0.25]
+                                      [--photo [--supersample 4 --width 1 --ambient 0.3]]
     python PMVO.py --yaml=configs/reconstruct/synthetic_hair
     python HairGrow.py --yaml=configs/reconstruct/synthetic_hair
     python -m monohair_amd.hairmetrics data/synthetic_hair/output/10-16/refine/connected_strands.hair \
@@ -13,8 +14,10 @@ on-disk case in the reference's layout with the ground truth next to it:
 The reference has no counterpart.  The capture rule is written out in include/mh_pmvo.h ("Hair capture") and restated in
 numpy by tests/hair_capture_np.py; the kernels are csrc/haircapture.hip.  Hair is sub-pixel thin, so a pixel accumulates the
 doubled-angle directions of all the strand samples near its front layer: where strands cross the confidence drops, as a Gabor
-bank's would.  There is no CPU path for the renderer; the strand model is host code (numpy, libm: the same arrays for the same
-seed on one host, not bit for bit between hosts)."""
+bank's would.  With --photo the capture is made of photographs instead (photo_planes: the "Hair photograph" rule of the same
+header, restated by tests/hair_photo_np.py): capture_images/ holds shaded, anti-aliased gray pictures of the strands, and
+best_ori/ and conf/ are what the Gabor stage makes of them.  There is no CPU path for the renderer; the strand model is host
+code (numpy, libm: the same arrays for the same seed on one host, not bit for bit between hosts)."""
 import argparse
 import ctypes
 import json
@@ -34,6 +37,13 @@ BUST_R = 0.09          # its bust sphere (bust_long_tsfm.obj)
 CAP_Y_MIN = 0.03       # the scalp cap: the part of the sphere with y >= this
 CLEARANCE = 0.0005     # every point after the root stays at least this far outside the head
 MAX_COLMAP_POINTS = 200000
+# the photograph's defaults (what was tried): a strand 3 of 4 sub-pixels wide, a head light
+PHOTO_SUPERSAMPLE = 4
+PHOTO_WIDTH = 1
+PHOTO_AMBIENT = 0.3
+PHOTO_ALBEDO = (0.35, 1.0)
+PHOTO_BUST_CODE = 64
+PHOTO_BACKGROUND_CODE = 32
 
 
 def code_table():
@@ -173,6 +183,95 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
     return depth, ori, conf, mask
 
 
+def strand_albedo(n_strands, seed=0, lo=PHOTO_ALBEDO[0], hi=PHOTO_ALBEDO[1]):
+    """float32 [n_strands], uniform in [lo, hi]: the per-strand albedo table mh_photo_shade is handed (host numpy in float64,
+    rounded once; a stream of its own, so a strand's albedo says nothing about where make_hairstyle(seed=seed) rooted it)."""
+    if not 0.0 <= float(lo) <= float(hi) <= 1.0:
+        raise ValueError("0 <= lo <= hi <= 1")
+    return np.random.default_rng([int(seed), 1]).uniform(float(lo), float(hi), int(n_strands)).astype(np.float32)
+
+
+def _records(camera):
+    return np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
+
+
+def light_directions(camera):
+    """float64 [V,3], unit length: per view the world direction towards the camera -- the third row of the rotation of its
+    world-to-camera pose (the camera looks down -z), normalised -- a head light."""
+    r = _records(camera)[:, 8:11].astype(np.float64)
+    return r / np.sqrt((r * r).sum(1))[:, None]
+
+
+def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHOTO_WIDTH, ambient=PHOTO_AMBIENT, albedo=None,
+                 seed=0, bust=None, bust_code=PHOTO_BUST_CODE, background_code=PHOTO_BACKGROUND_CODE, light=None,
+                 device="cuda:0", return_details=False, pixel_center=0.0):
+    """strands = (counts, points); camera as for capture_planes -> uint8 [V,H,W] device tensor: the gray photographs of the
+    strand set by the photograph rule of include/mh_pmvo.h.  albedo: float32 [n_strands] (default strand_albedo(n_strands,
+    seed)); light: float64 [V,3] unit vectors (default light_directions(camera)); bust = (vertices, faces): the occluder, drawn
+    as capture_planes draws it and shown as bust_code.  With return_details a second value: per view a dict of vert, valid,
+    shade (uint8 [n_points]: entry i is segment (i, i+1)), keys (int64 tensor holding the unsigned 64-bit key plane
+    [S H, S W]), cover (int32 [H,W]), dropped (int), depth0 (or None)."""
+    if not torch.cuda.is_available():
+        raise _lib.MhError("monohair_amd.synth_hair needs a ROCm GPU: the renderer has no CPU fallback")
+    device = torch.device(device)
+    H, W, ss, width = int(H), int(W), int(supersample), int(width)
+    counts, offs_h, pts_h = _strands(strands)
+    S, n = int(counts.shape[0]), int(pts_h.shape[0])
+    recs = _records(camera)
+    V = recs.shape[0]
+    albedo_h = strand_albedo(S, seed) if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(-1)
+    if albedo_h.shape[0] != S or not (np.isfinite(albedo_h).all() and (albedo_h >= 0).all()):
+        raise ValueError("albedo: one finite value >= 0 per strand")
+    light_h = np.ascontiguousarray(light_directions(recs) if light is None else light, dtype=np.float64).reshape(-1, 3)
+    if light_h.shape[0] != V:
+        raise ValueError("light: one direction per view")
+    L, ctx = _lib.lib(), _ctx_for(device)
+    need = int(L.mh_photo_scratch_bytes(n, H, W, ss))
+    if need == 0:
+        raise ValueError("photo_planes: supersample in {1, 2, 4, 8} and supersample^2 * H * W < 2^31")
+    with torch.cuda.device(device):
+        st = _lib.stream_ptr()
+        pts = torch.from_numpy(pts_h).to(device)
+        offs = torch.from_numpy(offs_h).to(device)
+        alb = torch.from_numpy(albedo_h if S else np.zeros(1, np.float32)).to(device)
+        gray = torch.empty((V, H, W), dtype=torch.uint8, device=device)
+        renderer = None
+        if bust is not None:
+            from .render import DepthRenderer
+
+            renderer = DepthRenderer([bust], device)
+        details = []
+        scratch = None if return_details else torch.empty(need, dtype=torch.uint8, device=device)
+        for v in range(V):
+            d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
+            if not return_details:
+                _lib.check(L.mh_photo_view(ctx, _hp(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, _lib.ptr(alb),
+                                           _hp(light_h[v]), float(ambient), H, W, ss, width, _lib.ptr(d0), int(bust_code),
+                                           int(background_code), _lib.ptr(scratch), scratch.numel(), _lib.ptr(gray[v]), None,
+                                           st), "mh_photo_view")
+                continue
+            vert = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
+            valid = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+            shade = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+            keys = torch.empty((ss * H, ss * W), dtype=torch.int64, device=device)
+            cover = torch.empty((H, W), dtype=torch.int32, device=device)
+            dropped = torch.empty(1, dtype=torch.int32, device=device)
+            _lib.check(L.mh_capture_project(ctx, _hp(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
+                       "mh_capture_project")
+            _lib.check(L.mh_photo_shade(ctx, _lib.ptr(pts), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(alb),
+                                        _hp(light_h[v]), float(ambient), _lib.ptr(shade), st), "mh_photo_shade")
+            _lib.check(L.mh_photo_front(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(shade), H, W, ss,
+                                        width, _lib.ptr(d0), _lib.ptr(keys), _lib.ptr(dropped), st), "mh_photo_front")
+            _lib.check(L.mh_photo_resolve(ctx, _lib.ptr(keys), _lib.ptr(d0), H, W, ss, int(bust_code), int(background_code),
+                                          _lib.ptr(gray[v]), _lib.ptr(cover), st), "mh_photo_resolve")
+            details.append(dict(vert=vert[:n], valid=valid[:n], shade=shade[:n], keys=keys, cover=cover,
+                                dropped=int(dropped.item()), depth0=d0))
+        torch.cuda.current_stream().synchronize()      # (the occluder plane and the scratch are read asynchronously)
+    if return_details:
+        return gray, details
+    return gray
+
+
 def write_geometry(base, strands, cams, seed=0):
     """The files of a case that need no GPU, under the case directory `base`: ours/cam_params.json, the bust and scalp
     spheres of synth.write_case (the scalp with `vn` records), ours/colmap_points.obj -- a vertices-only OBJ of the strand
@@ -196,12 +295,16 @@ def write_geometry(base, strands, cams, seed=0):
 
 
 def write_case(root, case="synthetic_hair", V=24, H=480, W=270, seed=0, n_strands=2000, n_points=64, strands=None, radius=1,
-               tol=0.25, scale=1.7, rings=1, device="cuda:0"):
+               tol=0.25, scale=1.7, rings=1, device="cuda:0", photo=False, supersample=PHOTO_SUPERSAMPLE, width=PHOTO_WIDTH,
+               ambient=PHOTO_AMBIENT):
     """Write a complete on-disk capture of a strand set in the layout of synth.write_case, so that
     `python PMVO.py --yaml=configs/reconstruct/<case>` and `python HairGrow.py ...` run on it through the real loaders:
       the files of write_geometry, capture_images/<view>.png, render_depth/<view>.npy [H,W,3] f32, best_ori/<view>.png (u8
       degrees), conf/<view>.png (u8), hair_mask/<view>.png.
-    strands = (counts, points) renders that set instead of make_hairstyle(n_strands, n_points, seed).  -> the case directory"""
+    strands = (counts, points) renders that set instead of make_hairstyle(n_strands, n_points, seed).
+    photo: capture_images/<view>.png are photographs (photo_planes; mode L), best_ori/, conf/ and Ori/ are what the Gabor
+    stage makes of them through its file path (gabor.batch_generate), and the geometric codes go to gt_best_ori/ and
+    gt_conf/; depth and hair mask stay geometric.  -> the case directory"""
     from PIL import Image
 
     base = os.path.join(root, case)
@@ -215,13 +318,25 @@ def write_case(root, case="synthetic_hair", V=24, H=480, W=270, seed=0, n_strand
     depth, ori, conf, mask = capture_planes((counts, points), cameras_from_list(cams), H, W, radius=radius, tol=tol,
                                             bust=bust, device=device)
     depth, ori, conf, mask = (t.cpu().numpy() for t in (depth, ori, conf, mask))
+    ori_dir, conf_dir, image = "best_ori", "conf", conf
+    if photo:
+        ori_dir, conf_dir = "gt_best_ori", "gt_conf"
+        for d in (ori_dir, conf_dir):
+            os.makedirs(os.path.join(base, d), exist_ok=True)
+        image = photo_planes((counts, points), cameras_from_list(cams), H, W, supersample=supersample, width=width,
+                             ambient=ambient, seed=seed, bust=bust, device=device).cpu().numpy()
     for i, cam in enumerate(cams):
         name = cam["file"]
         np.save(os.path.join(base, "render_depth", name + ".npy"), np.repeat(depth[i][..., None], 3, axis=2))
-        Image.fromarray(ori[i]).save(os.path.join(base, "best_ori", name + ".png"))
-        Image.fromarray(conf[i]).save(os.path.join(base, "conf", name + ".png"))
+        Image.fromarray(ori[i]).save(os.path.join(base, ori_dir, name + ".png"))
+        Image.fromarray(conf[i]).save(os.path.join(base, conf_dir, name + ".png"))
         Image.fromarray(np.repeat(mask[i][..., None], 3, axis=2)).save(os.path.join(base, "hair_mask", name + ".png"))
-        Image.fromarray(conf[i]).save(os.path.join(base, "capture_images", name + ".png"))
+        Image.fromarray(image[i]).save(os.path.join(base, "capture_images", name + ".png"))
+    if photo:
+        from . import gabor
+
+        with torch.cuda.device(torch.device(device)):
+            gabor.batch_generate(base, "capture_images")       # the shipped stage through its file path
     return base
 
 
@@ -245,6 +360,12 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--radius", type=int, default=1)
     ap.add_argument("--tol", type=float, default=0.25)
+    ap.add_argument("--photo", action="store_true",
+                    help="capture_images/ are rendered photographs and best_ori/, conf/ come from the Gabor stage run on them "
+                         "(the geometric codes go to gt_best_ori/, gt_conf/)")
+    ap.add_argument("--supersample", type=int, default=PHOTO_SUPERSAMPLE, choices=(1, 2, 4, 8))
+    ap.add_argument("--width", type=int, default=PHOTO_WIDTH, help="half-width of a strand in sub-pixels")
+    ap.add_argument("--ambient", type=float, default=PHOTO_AMBIENT)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     strands = None
@@ -253,7 +374,8 @@ def main(argv=None):
         strands = (np.asarray(segments, np.int64), points.astype(np.float32))
     base = write_case(args.root, args.case, V=args.views, H=args.size[0], W=args.size[1], seed=args.seed,
                       n_strands=args.strands, n_points=args.points, strands=strands, radius=args.radius, tol=args.tol,
-                      device=args.device)
+                      device=args.device, photo=args.photo, supersample=args.supersample, width=args.width,
+                      ambient=args.ambient)
     print("wrote %s (ground truth: %s)" % (base, os.path.join(base, "gt_strands.hair")))
     return 0
 
