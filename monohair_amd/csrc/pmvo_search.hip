@@ -429,12 +429,69 @@ struct MhCascS {
     __device__ __forceinline__ float done() const { return BIG ? (a0 + a1) + a2 : (a0 + a1); }
 };
 
+// Inclusive prefix sum over the 64 lanes of a wave in the VALU's data path (DPP): four shifts inside every row of 16 lanes, then
+// lane 15 of a row into the next row and lane 31 into the upper half -- no LDS round trip (six ds_bpermute_b32, each waited
+// for, as __shfl_up gives it).  A lane a shift has no source for, and a row a broadcast is not meant for, adds 0.
+__device__ __forceinline__ int mh_wave_prefix_sum(int x) {
+#define MH_DPP_ADD(CTRL, ROWS) x += __builtin_amdgcn_update_dpp(0, x, CTRL, ROWS, 0xF, false)
+    MH_DPP_ADD(0x111, 0xF);   // row_shr:1
+    MH_DPP_ADD(0x112, 0xF);   // row_shr:2
+    MH_DPP_ADD(0x114, 0xF);   // row_shr:4
+    MH_DPP_ADD(0x118, 0xF);   // row_shr:8
+    MH_DPP_ADD(0x142, 0xA);   // row_bcast:15 into rows 1 and 3
+    MH_DPP_ADD(0x143, 0xC);   // row_bcast:31 into rows 2 and 3
+#undef MH_DPP_ADD
+    return x;
+}
+
+// One wave copies a tap list from global memory to dst in LDS (dst wave-uniform, both 16-byte aligned) with loads that write
+// LDS themselves (global_load_lds_dwordx4: lane i's 16 bytes land at dst + 16 * i, no register result, no ds_write; retired
+// by vmcnt): one instruction per 64 records, none of them waited for here -- the caller's next __syncthreads() is the wait.
+// Records [0, nrec) come from src, records [nrec, nfill) are the neutral (0, 0) taps behind a key-body list
+// (mh_key_staged), read from one zero record in global memory: an ordinary LDS store of zeros beside the copies in flight
+// makes the compiler wait for every one of them first.
+__device__ const float4 mh_zero_tap = {0.0f, 0.0f, 0.0f, 0.0f};
+__device__ __forceinline__ void mh_stage_list(const float4 *__restrict__ src, float4 *dst, int nrec, int nfill, int lane) {
+    for (int i0 = 0; i0 < nfill; i0 += 64) {
+        const int i = i0 + lane;
+        if (i < nfill) {
+            const float4 *g = (i < nrec) ? src + i : &mh_zero_tap;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
+                                             (__attribute__((address_space(3))) void *)(dst + i0), 16, 0, 0);
+        }
+    }
+}
+
+// Records of a list of c taps in LDS: header + taps (KEYS: behind the taps of a list that goes through the key body, the
+// neutral (0, 0) records that fill its last block -- mh_key_staged); 0 for a view that does not see the point.
+template <bool KEYS, bool BIGP>
+__device__ __forceinline__ int mh_list_records(int c) {
+    return c ? ((KEYS && c > MH_KEY_MIN_TAPS) ? mh_key_staged<BIGP>(c) : c) + 1 : 0;
+}
+// One batch of a 64-view block (views vb + the set bits of take; lane b holds view vb + b's taps c, records len and the
+// inclusive prefix sum pre of len; base = records of the block's earlier batches): this wave issues the copies of the
+// wave-th, wave + 4-th, ... list of the batch (a lane's place among the set bits of take), all in flight together.
+template <int T, bool KEYS>
+__device__ __forceinline__ void mh_stage_batch(const float4 *__restrict__ taps, float4 *s_taps, int vb, int n, int N, int P1,
+                                               int c, int len, int pre, int base, unsigned long long take, int lane, int wave) {
+    const unsigned place = __builtin_amdgcn_mbcnt_hi((unsigned)(take >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)take, 0u));
+    unsigned long long m = take & __ballot((int)(place & (T / 64 - 1)) == wave);
+    while (m) {
+        const int b = (int)__builtin_ctzll(m);
+        m &= m - 1;
+        const int L = __builtin_amdgcn_readlane(len, b);
+        const int off = __builtin_amdgcn_readlane(pre, b) - L - base;
+        const int lr = KEYS ? __builtin_amdgcn_readlane(c, b) + 1 : L;   // records the list really has
+        mh_stage_list(taps + ((size_t)(vb + b) * N + n) * P1, s_taps + off, lr, L, lane);
+    }
+}
+
 template <int KA, int T, bool BIGV, bool KEYS, bool BIGP>
 __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const float *__restrict__ offs, int S,
                                                      int n, int N, int P1, float thr,
                                                      const float4 *__restrict__ taps, const uint8_t *__restrict__ vcnt,
                                                      int nact, int tid, float *s_loss, uint8_t *s_pos, float4 *s_taps,
-                                                     const float4 *s_rank, int c_first) {
+                                                     const float4 *s_rank, int c_first, int pre_first) {
     constexpr int KN = KA > 0 ? KA : 1;   // a wave without items (KA == 0) only helps to stage the lists
     constexpr int KM = KA;
     const int V = vw.V;
@@ -630,48 +687,27 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
             cnt[j] += (w > 0.0f) ? 1 : 0;
         }
     };
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int vb = 0; vb < V; vb += 64) {
         const int vv = vb + lane;
         // list length of view vv (0: the view does not see the point); the first block's was requested in the kernel's
         // prologue, in front of the first barrier
         const int c = vb == 0 ? c_first : ((vv < V) ? (int)vcnt[(size_t)vv * N + n] : 0);
-        // records: header + taps (KEYS: behind the taps of a list that goes through the key body, the neutral (0, 0) records
-        // that fill its last block -- mh_key_staged)
-        const int len = c ? ((KEYS && c > MH_KEY_MIN_TAPS) ? mh_key_staged<BIGP>(c) : c) + 1 : 0;
-        int pre = len;                                               // inclusive prefix sum over the lanes
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(pre, o);
-            pre += (lane >= o) ? y : 0;
-        }
+        const int len = mh_list_records<KEYS, BIGP>(c);
+        // inclusive prefix sum over the lanes (the first block's comes from the prologue, which staged that block's first
+        // batch in front of its barrier)
+        const int pre = vb == 0 ? pre_first : mh_wave_prefix_sum(len);
+        bool staged = vb == 0;
         unsigned long long todo = __ballot(c != 0);
         int base = 0;
         while (todo) {
             // the next lists that fit together (pre is monotone: a prefix of the views left; one list always fits)
             const unsigned long long take = todo & __ballot(pre - base <= MH_S3_CAP);
-            {
-                unsigned long long m = take;
-                int k = 0;
-                while (m) {
-                    const int b = (int)__builtin_ctzll(m);
-                    m &= m - 1;
-                    if ((k & (T / 64 - 1)) == wave) {
-                        const int L = __builtin_amdgcn_readlane(len, b);
-                        const int off = __builtin_amdgcn_readlane(pre, b) - L - base;
-                        const float4 *__restrict__ src = taps + ((size_t)(vb + b) * N + n) * P1;
-                        if constexpr (KEYS) {
-                            const int lr = __builtin_amdgcn_readlane(c, b) + 1;   // records the list really has
-                            for (int i = lane; i < L; i += 64)
-                                s_taps[off + i] = (i < lr) ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-                        } else {
-                            for (int i = lane; i < L; i += 64) s_taps[off + i] = src[i];
-                        }
-                    }
-                    ++k;
-                }
+            if (!staged) {
+                mh_stage_batch<T, KEYS>(taps, s_taps, vb, n, N, P1, c, len, pre, base, take, lane, wave);
+                __syncthreads();   // (waits for the copies: they count on vmcnt, and the barrier's fence drains it)
             }
-            __syncthreads();
+            staged = false;
             if constexpr (KA > 0) {
                 unsigned long long m = take;
                 while (m) {
@@ -741,6 +777,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     // chain of loads per lane, all ranks in parallel (a scalar loop over base_view_conf first cost five more round trips
     // before the workgroup's first barrier)
     const int c_first = ((tid & 63) < vw.V) ? (int)vcnt[(size_t)(tid & 63) * N + n] : 0;   // (see mh_search_slices_lds)
+    // the first batch of the first 64-view block goes to LDS from here (mh_search_slices_lds has the batches): the copies are
+    // in flight while the rank records are made, and the barrier behind those waits for both
+    const int len_first = mh_list_records<KEYS, BIGP>(c_first);
+    const int pre_first = mh_wave_prefix_sum(len_first);
+    mh_stage_batch<T, KEYS>(taps, s_taps, 0, n, N, P1, c_first, len_first, pre_first, 0,
+                            __ballot(c_first != 0) & __ballot(pre_first <= MH_S3_CAP), tid & 63,
+                            __builtin_amdgcn_readfirstlane(tid >> 6));
     if (tid == 64) s_tail = mh_tail_from(rule, n, S);
     if (tid < nrank) {
         const size_t ro = (size_t)(tid * rank_step) * N + n;
@@ -760,7 +803,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     const int wave0 = tid & ~63;   // first item of this wave in slice 0
     int ka = 0;
     for (int j = 0; j < 4; ++j) ka += (j * T + wave0 < nact) ? 1 : 0;
-#define MH_S3_ARGS vw, offs, S, n, N, P1, thr, taps, vcnt, nact, tid, s_loss, s_pos, s_taps, s_rank, c_first
+#define MH_S3_ARGS vw, offs, S, n, N, P1, thr, taps, vcnt, nact, tid, s_loss, s_pos, s_taps, s_rank, c_first, pre_first
     if (ka == 4) mh_search_slices_lds<4, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
     else if (ka == 3) mh_search_slices_lds<3, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
     else if (ka == 2) mh_search_slices_lds<2, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
