@@ -613,6 +613,60 @@ int mh_photo_view(mh_ctx *ctx, const float *cam_host, const float *points, const
                   int width, const float *depth0, int bust_code, int background_code, void *scratch, size_t scratch_bytes,
                   uint8_t *gray_u8, int32_t *cover, void *stream);
 
+/* Strand volume (monohair_amd.hairvolume; no counterpart in the reference): a strand set turned into the volume the fit of
+ * refine would ideally produce -- the occupied voxels with one direction each, in PMVO's own voxel conventions -- so that the
+ * strand stage can be run on a perfect volume and a fitted volume can be scored.  points [n_points,3] float32 in `.hair`
+ * coordinates (world minus bust_to_origin), offsets [n_strands+1] (int64, the exclusive scan of the per-strand point counts);
+ * bust_to_origin [3], voxel_min [3] and voxel_size are HOST float64 (finite, voxel_size > 0), dims = (X, Y, Z) HOST int32 with
+ * X*Y*Z < 2^31; 1 <= sub <= 16 samples per voxel of travel.  Everything is float64 arithmetic on the float32 values, + - * /
+ * sqrt in the order written, nothing fused.  The rule:
+ *
+ * Vertex.  w = p + bust_to_origin; voxel coordinate g = ((w.x - vmin.x)/vs, ((-w.y) - vmin.y)/vs, ((-w.z) - vmin.z)/vs): p2v
+ *   before rounding (Utils/PMVO_utils.py:386-404).  A vertex is valid iff all three are finite.
+ * Segment (a, b) = consecutive points of one strand, both valid; any other pair makes nothing.  d = g_b - g_a; n = max(1,
+ *   ceil(sub * max(|d.x|, |d.y|, |d.z|))); a segment with n > 8192 is dropped and counted (dropped_segments).  Direction, in
+ *   WORLD space as the fit stores it: e = w_b - w_a, len = sqrt((e.x*e.x + e.y*e.y) + e.z*e.z), u = e / len, q = rint(4096 * u)
+ *   per component, half to even, as integers; q = 0 when len is 0 (or not finite).
+ * Sample j = 0 .. n-1: t = (j + 0.5)/n; voxel = rint(g_a + t*d) per component, half to even.  A sample whose voxel lies outside
+ *   [0,X) x [0,Y) x [0,Z) is dropped and counted (outside_samples), not clamped.  Each kept sample adds to its voxel cnt += 1 and
+ *   the six products qx*qx, qy*qy, qz*qz, qx*qy, qx*qz, qy*qz (int64).  Integer sums: the result does not depend on the order
+ *   of arrival.
+ * Resolve, per voxel with cnt > 0.  A voxel with cnt > 2^29 is refused (|q| <= 4096: up to there every sum stays within 2^53
+ *   and converts to float64 exactly).  M = the symmetric 3x3 of the six sums as float64; trace = (Mxx + Myy) + Mzz.  If trace
+ *   = 0: ori = 0, coh = 0 (occupied, no direction).  Otherwise v = the column of M with the largest diagonal entry, the first
+ *   on ties; 24 times y = M v, each row as (a*v.x + b*v.y) + c*v.z, then v = y / sqrt((y.x*y.x + y.y*y.y) + y.z*y.z); then
+ *   coh = ((v.x*y.x + v.y*y.y) + v.z*y.z) / trace with y = M v once more; if v.y > 0, v = -v (the fit's canonical sign,
+ *   PMVO.py:702-703); ori = float32(v).
+ *
+ * mh_strand_volume_accumulate: acc [X*Y*Z][8] int64 = per voxel (x*Y + y)*Z + z {cnt, xx, yy, zz, xy, xz, yz, unused} and occ
+ *   [X*Y*Z] uint8 = 1 where cnt > 0 (both are zeroed first); counters (device int64 [2]) = {dropped_segments, outside_samples}.
+ * mh_strand_volume_resolve: index [n_voxels] int32 = the occupied voxels ascending (mh_select_rows on occ) -> voxels [n_voxels,3]
+ *   int64 (x, y, z), the order mh_voxel_group's fit returns; ori [n_voxels,3] float32, cnt [n_voxels] int32, coh [n_voxels]
+ *   float64, sums [n_voxels,6] int64 (optional: the six sums); refused (device int32) = the voxels over the cnt bound, whose
+ *   outputs are zero.
+ *
+ * Volume scores: one sparse volume against another on the same grid.  A query voxel with float32 direction a has bit k set iff
+ * some target voxel lies within Chebyshev distance reach[k] of it (|dx|, |dy|, |dz| <= reach[k]; neighbours outside the grid
+ * do not exist) whose float32 direction b passes: cos2[k] < 0 (no direction test), or, in float64, dot = (a.x*b.x + a.y*b.y) +
+ * a.z*b.z, na = (a.x*a.x + a.y*a.y) + a.z*a.z, nb likewise, na > 0 and nb > 0 and dot*dot >= cos2[k] * (na*nb).  reach (int32,
+ * 0..4) and cos2 (float64) are HOST arrays of n_pairs <= 8.  Precision = matched predicted voxels / predicted voxels, recall
+ * the same query the other way round; the flags are counted by mh_flag_counts.
+ * mh_volume_index: voxels [n_voxels,3] int64 -> index [X*Y*Z] int32 = the row of the voxel at (x*Y + y)*Z + z, -1 where there
+ *   is none; status (device int32 [2]) = {voxels outside the grid, voxels listed more than once}: either makes the list
+ *   unusable (the caller raises).
+ * mh_volume_match: out_flags [nq] uint8 for the queries (q_voxels, q_ori) against the targets (t_index, t_ori [n_targets,3]). */
+int mh_strand_volume_accumulate(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands, int n_points,
+                                const double *bust_to_origin, const double *voxel_min, double voxel_size, const int32_t *dims,
+                                int sub, long long *acc, uint8_t *occ, long long *counters, void *stream);
+int mh_strand_volume_resolve(mh_ctx *ctx, const long long *acc, const int32_t *index, int n_voxels, const int32_t *dims,
+                             long long *voxels, float *ori, int32_t *cnt, double *coh, long long *sums, int32_t *refused,
+                             void *stream);
+int mh_volume_index(mh_ctx *ctx, const long long *voxels, int n_voxels, const int32_t *dims, int32_t *index, int32_t *status,
+                    void *stream);
+int mh_volume_match(mh_ctx *ctx, const long long *q_voxels, const float *q_ori, int nq, const int32_t *t_index,
+                    const float *t_ori, const int32_t *dims, const int32_t *reach, const double *cos2, int n_pairs,
+                    uint8_t *out_flags, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

@@ -90,6 +90,10 @@ _SIGS = {
     "mh_photo_resolve": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
     "mh_photo_view": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, ci, ci, ci, ci, vp, ci, ci, vp, csz, vp, vp,
                            vp]),
+    "mh_strand_volume_accumulate": (ci, [vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, vp, ci, vp, vp, vp, vp]),
+    "mh_strand_volume_resolve": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mh_volume_index": (ci, [vp, vp, ci, vp, vp, vp, vp]),
+    "mh_volume_match": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]),
     "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

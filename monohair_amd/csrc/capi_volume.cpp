@@ -1,0 +1,72 @@
+// capi_volume.cpp -- C ABI of the strand volume and the volume scores (csrc/hairvolume.hip; no counterpart in the reference)
+#include <cmath>
+
+#include "mh_capi.h"
+
+static bool vol_dims_ok(const int32_t *dims) { return dims && cells_fit_int32(dims[0], dims[1], dims[2]); }
+
+extern "C" int mh_strand_volume_accumulate(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands,
+                                           int n_points, const double *bust_to_origin, const double *voxel_min,
+                                           double voxel_size, const int32_t *dims, int sub, long long *acc, uint8_t *occ,
+                                           long long *counters, void *stream) {
+    if (!ctx || !bust_to_origin || !voxel_min || !vol_dims_ok(dims) || !acc || !occ || !counters || n_strands < 0 ||
+        n_points < 0 || (n_points > 0 && (!points || !offsets || n_strands < 1)) || sub < 1 || sub > 16 ||
+        !(voxel_size > 0.0 && std::isfinite(voxel_size)))
+        return fail(MH_ERR_ARG, "mh_strand_volume_accumulate: bad arguments");
+    MhVolGrid gr;
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(bust_to_origin[c]) || !std::isfinite(voxel_min[c]))
+            return fail(MH_ERR_ARG, "mh_strand_volume_accumulate: bust_to_origin and voxel_min must be finite");
+        gr.bust[c] = bust_to_origin[c], gr.vmin[c] = voxel_min[c];
+    }
+    gr.vs = voxel_size;
+    gr.X = dims[0], gr.Y = dims[1], gr.Z = dims[2];
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_volume_accum(points, (const int64_t *)offsets, n_strands, n_points, gr, sub,
+                                                  (unsigned long long *)acc, occ, (unsigned long long *)counters,
+                                                  (hipStream_t)stream),
+                    "mh_strand_volume_accumulate");
+}
+
+extern "C" int mh_strand_volume_resolve(mh_ctx *ctx, const long long *acc, const int32_t *index, int n_voxels,
+                                        const int32_t *dims, long long *voxels, float *ori, int32_t *cnt, double *coh,
+                                        long long *sums, int32_t *refused, void *stream) {
+    if (!ctx || !acc || !vol_dims_ok(dims) || !refused || n_voxels < 0 ||
+        (n_voxels > 0 && (!index || !voxels || !ori || !cnt || !coh)))
+        return fail(MH_ERR_ARG, "mh_strand_volume_resolve: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_strand_volume_resolve(acc, index, n_voxels, dims[1], dims[2], voxels, ori, cnt, coh, sums,
+                                                    refused, (hipStream_t)stream),
+                    "mh_strand_volume_resolve");
+}
+
+extern "C" int mh_volume_index(mh_ctx *ctx, const long long *voxels, int n_voxels, const int32_t *dims, int32_t *index,
+                               int32_t *status, void *stream) {
+    if (!ctx || !vol_dims_ok(dims) || !index || !status || n_voxels < 0 || (n_voxels > 0 && !voxels))
+        return fail(MH_ERR_ARG, "mh_volume_index: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_volume_index(voxels, n_voxels, dims[0], dims[1], dims[2], index, status, (hipStream_t)stream),
+                    "mh_volume_index");
+}
+
+extern "C" int mh_volume_match(mh_ctx *ctx, const long long *q_voxels, const float *q_ori, int nq, const int32_t *t_index,
+                               const float *t_ori, const int32_t *dims, const int32_t *reach, const double *cos2, int n_pairs,
+                               uint8_t *out_flags, void *stream) {
+    if (nq == 0) return MH_OK;
+    if (!ctx || !q_voxels || !q_ori || nq < 0 || !t_index || !vol_dims_ok(dims) || !reach || !cos2 || n_pairs < 1 ||
+        n_pairs > MH_VOL_MAXK || !out_flags)
+        return fail(MH_ERR_ARG, "mh_volume_match: bad arguments");
+    MhVolPairs pr;
+    pr.K = n_pairs;
+    for (int k = 0; k < MH_VOL_MAXK; ++k) {
+        pr.reach[k] = k < n_pairs ? reach[k] : 0;
+        pr.cos2[k] = k < n_pairs ? cos2[k] : 0.0;
+        if (k < n_pairs && (reach[k] < 0 || reach[k] > MH_VOL_MAXREACH || std::isnan(cos2[k])))
+            return fail(MH_ERR_ARG, "mh_volume_match: pair %d: reach %d (0..%d), cos2 %g", k, reach[k], MH_VOL_MAXREACH,
+                        cos2[k]);
+    }
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_volume_match(q_voxels, q_ori, nq, t_index, t_ori, dims[0], dims[1], dims[2], pr, out_flags,
+                                           (hipStream_t)stream),
+                    "mh_volume_match");
+}

@@ -46,6 +46,21 @@ struct MhCapTable {                   // float32 (cos 2 theta_k, sin 2 theta_k) 
     float t[180][2];
 };
 
+#define MH_VOL_MAXN 8192              // strand volume: a segment of more samples than this is dropped and counted
+#define MH_VOL_MAXCNT (1ll << 29)     // ... and a voxel of more samples than this is refused: |q| <= 4096, so every sum stays
+                                      // within 2^29 * 2^24 = 2^53 and converts to float64 exactly
+struct MhVolGrid {                    // the voxel grid of PMVO's volume, by value (all host values)
+    double bust[3], vmin[3], vs;
+    int X, Y, Z;
+};
+#define MH_VOL_MAXK 8                 // threshold pairs of one mh_volume_match launch: one bit each of the flag byte
+#define MH_VOL_MAXREACH 4
+struct MhVolPairs {                   // pair k: Chebyshev radius in voxels, squared-cosine bound (< 0: no direction test)
+    double cos2[MH_VOL_MAXK];
+    int reach[MH_VOL_MAXK];
+    int K;
+};
+
 struct MhRVert;    // raster.hip: a transformed mesh vertex (16 B)
 struct MhRLVert;   // raster.hip: a transformed strand vertex (32 B)
 
@@ -290,4 +305,14 @@ int mh_launch_photo_front(const float *vert, const uint8_t *valid, const int64_t
                           unsigned long long *keys, int32_t *dropped, hipStream_t st);
 int mh_launch_photo_resolve(const unsigned long long *keys, const float *depth0, int H, int W, int ss, int bust_code,
                             int background_code, uint8_t *gray, int32_t *cover, hipStream_t st);
+
+// ---- hairvolume.hip (loads with its first launch)
+int mh_launch_strand_volume_accum(const float *pts, const int64_t *offs, int S, int n_points, MhVolGrid gr, int sub,
+                                  unsigned long long *acc, uint8_t *occ, unsigned long long *counters, hipStream_t st);
+int mh_launch_strand_volume_resolve(const long long *acc, const int32_t *index, int G, int Y, int Z, long long *voxels,
+                                    float *ori, int32_t *cnt, double *coh, long long *sums, int32_t *refused, hipStream_t st);
+int mh_launch_volume_index(const long long *voxels, int G, int X, int Y, int Z, int32_t *index, int32_t *status,
+                           hipStream_t st);
+int mh_launch_volume_match(const long long *q_vox, const float *q_ori, int nq, const int32_t *t_index, const float *t_ori,
+                           int X, int Y, int Z, MhVolPairs pr, uint8_t *out, hipStream_t st);
 }
