@@ -444,6 +444,14 @@ __device__ __forceinline__ int mh_wave_prefix_sum(int x) {
     return x;
 }
 
+// the lane's index in its wave, made where it is asked for: what follows from it (an item, a global address) is then made
+// there too, and is not a register kept across the view loops
+__device__ __forceinline__ int mh_lane_now() {
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    return lane;
+}
+
 // One wave copies a tap list from global memory to dst in LDS (dst wave-uniform, both 16-byte aligned) with loads that write
 // LDS themselves (global_load_lds_dwordx4: lane i's 16 bytes land at dst + 16 * i, no register result, no ds_write; retired
 // by vmcnt): one instruction per 64 records, none of them waited for here -- the caller's next __syncthreads() is the wait.
@@ -468,30 +476,152 @@ template <bool KEYS, bool BIGP>
 __device__ __forceinline__ int mh_list_records(int c) {
     return c ? ((KEYS && c > MH_KEY_MIN_TAPS) ? mh_key_staged<BIGP>(c) : c) + 1 : 0;
 }
-// One batch of a 64-view block (views vb + the set bits of take; lane b holds view vb + b's taps c, records len and the
-// inclusive prefix sum pre of len; base = records of the block's earlier batches): this wave issues the copies of the
+// One batch of a 64-view block (views vb + the set bits of take; lane b holds view vb + b's taps c and the inclusive prefix
+// sum pre of the lists' records, mh_list_records(c); base = records of the block's earlier batches): this wave issues the copies of the
 // wave-th, wave + 4-th, ... list of the batch (a lane's place among the set bits of take), all in flight together.
-template <int T, bool KEYS>
+template <int T, bool KEYS, bool BIGP>
 __device__ __forceinline__ void mh_stage_batch(const float4 *__restrict__ taps, float4 *s_taps, int vb, int n, int N, int P1,
-                                               int c, int len, int pre, int base, unsigned long long take, int lane, int wave) {
+                                               int c, int pre, int base, unsigned long long take, int wave) {
+    const int lane = mh_lane_now();   // (the lists' global addresses are made per batch)
     const unsigned place = __builtin_amdgcn_mbcnt_hi((unsigned)(take >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)take, 0u));
     unsigned long long m = take & __ballot((int)(place & (T / 64 - 1)) == wave);
     while (m) {
         const int b = (int)__builtin_ctzll(m);
         m &= m - 1;
-        const int L = __builtin_amdgcn_readlane(len, b);
+        const int cb = __builtin_amdgcn_readlane(c, b);
+        const int L = mh_list_records<KEYS, BIGP>(cb);
         const int off = __builtin_amdgcn_readlane(pre, b) - L - base;
-        const int lr = KEYS ? __builtin_amdgcn_readlane(c, b) + 1 : L;   // records the list really has
+        const int lr = cb + 1;   // records the list really has
         mh_stage_list(taps + ((size_t)(vb + b) * N + n) * P1, s_taps + off, lr, L, lane);
     }
 }
 
-template <int KA, int T, bool BIGV, bool KEYS, bool BIGP>
+// ---------------------------------------------------------------------------------------------
+// The leftover items of a point: nact = nvalid * S items fill nact / 64 wave-slices and leave L = nact % 64 items (900 = 14
+// slices + 4).  As a slice of their own they cost a wave every tap block of every visible view with 64 - L idle lanes.  For
+// 0 < L <= MH_S3_LEFT_MAX they are not a slice: the workgroup's last wave -- which never has more full slices than any other --
+// evaluates them one (item, view) PAIR per lane, per staging batch, in front of the batch's closing barrier, from the lists
+// that are in LDS for the slices anyway (mh_left_batch), and adds a pair's terms up per item after the last batch
+// (mh_left_sums) in the order and with the cascade of the slices.  A lane walks its own view's list with the
+// compare-and-select arithmetic of the portable kernel (exact for every input: no key, no re-evaluation).
+// LDS: (loss, weight) per (leftover item, view), the batch's visible views by place, the visible views per 64-view block --
+// 4 640 B, 31 912 B per workgroup: five workgroups per CU as before.  Points with L * V > MH_S3_LEFT_PAIRS, L > MH_S3_LEFT_MAX
+// or more than 256 views (the BIGV kernels) keep the slice, and so does the select-only kernel: the lists of 8-bit maps hold
+// 2.5 taps on average, a slice costs little there and the pairs' fixed cost per pass lost 4 % (profiles/search_leftover.txt).
+// ---------------------------------------------------------------------------------------------
+#define MH_S3_LEFT_MAX 16      // 900, 450, 270 and 720 items leave 4, 2, 14 and 16; the next remainders (26, 28) are nearly half a slice
+#define MH_S3_LEFT_PAIRS 544   // (leftover item, view) pairs that fit: L = 4 up to 136 views, L = 16 up to 34
+struct MhLeft {
+    float2 *pair;                // [L][V] (min loss, confidence of its tap)
+    unsigned *view;              // [64] the batch's visible views by place: LDS record offset | taps << 11 | lane of the view << 18
+    unsigned long long *vis;     // [4] visible views of every 64-view block
+};
+
+// One staging batch (views vb + the set bits of take, lane b holding view vb + b's taps c, records len and prefix sum pre, as in
+// mh_search_slices_lds): the L leftover items x the batch's views, one pair per lane, lane = (place of the view << lg) | item
+// with 2^lg >= L, in as many passes as that takes.
+__device__ __forceinline__ void mh_left_batch(const float *__restrict__ cams, float Hf, float Wf, int V,
+                                                        const float *__restrict__ offs, int S, const float4 *s_rank,
+                                                        const float4 *s_taps, MhLeft lf, int nact, int L, int vb, int c,
+                                                        int len, int pre, int base, unsigned long long take) {
+    // (the lane and what follows from it -- the lane's item, its position -- are made here, per batch: hoisted in front of the
+    // view loops they would be registers the slices' tap loops do not have)
+    const int lane = mh_lane_now();
+    const unsigned place = __builtin_amdgcn_mbcnt_hi((unsigned)(take >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)take, 0u));
+    if ((take >> lane) & 1ull) lf.view[place] = (unsigned)(pre - len - base) | ((unsigned)c << 11) | ((unsigned)lane << 18);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const int nv = __popcll(take);
+    const int lg = L > 1 ? 32 - __builtin_clz((unsigned)(L - 1)) : 0;
+    const int i = lane & ((1 << lg) - 1);
+    const bool mine = i < L;
+    const int it = nact - L + (mine ? i : 0);
+    const int r = (int)(((unsigned)it * ((1u << 20) / (unsigned)S + 1u)) >> 20), s = it - r * S;   // (see mh_search_slices_lds)
+    float X0, X1, X2;
+    mh_sample_item(s_rank + 4 * r, offs[s], X0, X1, X2);
+    for (int k0 = 0; k0 < nv; k0 += 64 >> lg) {
+        const int k = k0 + (lane >> lg);
+        const bool act = mine && k < nv;
+        const unsigned e = lf.view[act ? k : k0];
+        const int v = vb + (int)((e >> 18) & 63u);
+        const int ntap = act ? (int)((e >> 11) & 127u) : 0;
+        const float4 *rec = s_taps + (e & 2047u);
+        const float4 hdr = rec[0];
+        float row, col, dx, dy;
+        mh_pixel_of(cams + v * MH_CAM_STRIDE, X0, X1, X2, Hf, Wf, row, col);
+        mh_unit2(row - hdr.z, col - hdr.w, dx, dy);
+        const float4 t0 = rec[1];
+        float ml = 1.0f - __builtin_fabsf(t0.x * dx + t0.y * dy), bc = t0.z;
+        // to the longest list among the lanes, four records in flight (up to three are read past a list's end: inside s_taps,
+        // like the slices' last prefetch group)
+        for (int t = 1; t < ntap; t += 4) {
+            float4 g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) g[u] = rec[1 + t + u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float l = 1.0f - __builtin_fabsf(g[u].x * dx + g[u].y * dy);
+                const bool upd = (t + u < ntap) && (l < ml);
+                ml = upd ? l : ml;
+                bc = upd ? g[u].z : bc;
+            }
+        }
+        if (act) lf.pair[i * V + v] = float2{ml, bc};
+    }
+}
+
+// After the last batch: lane i < L adds item nact - L + i's terms over the visible views in ascending order, flushing the
+// cascade at every multiple of 16 below V as the slices do (V <= 256: two levels), and writes the item's loss and flag.
+__device__ __forceinline__ void mh_left_sums(MhLeft lf, int V, int nact, int L, float thr, float *s_loss,
+                                                       uint8_t *s_pos) {
+    const int lane = mh_lane_now();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (lane >= L) return;
+    MhCascS<false> num, den;
+    int cnt = 0, nf = 16;
+    for (int vb = 0; vb < V; vb += 64) {
+        unsigned long long m = lf.vis[vb >> 6];
+        while (m) {   // four views' terms in flight
+            int v[4];
+            float2 e[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u] = m ? vb + (int)__builtin_ctzll(m) : -1;
+                m &= m - 1;
+                e[u] = lf.pair[lane * V + (v[u] < 0 ? 0 : v[u])];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (v[u] < 0) break;
+                for (; nf <= v[u]; nf += 16) {
+                    num.flush(nf);
+                    den.flush(nf);
+                }
+                const float w = e[u].y;   // (vis != -1) * best_conf
+                num.a0 = num.a0 + e[u].x * w;
+                den.a0 = den.a0 + w;
+                cnt += (w > 0.0f) ? 1 : 0;
+            }
+        }
+    }
+    for (; nf <= V - 1; nf += 16) {
+        num.flush(nf);
+        den.flush(nf);
+    }
+    const int it = nact - L + lane;
+    const float dn = den.done();
+    const float nm = num.done();
+    const float ratio = dn / (float)cnt;
+    s_pos[it] = (ratio > thr) ? 1 : 0;
+    s_loss[it] = nm / dn;
+}
+
+template <int KA, int T, bool BIGV, bool KEYS, bool BIGP, bool LEFT = false>
 __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const float *__restrict__ offs, int S,
                                                      int n, int N, int P1, float thr,
                                                      const float4 *__restrict__ taps, const uint8_t *__restrict__ vcnt,
                                                      int nact, int tid, float *s_loss, uint8_t *s_pos, float4 *s_taps,
-                                                     const float4 *s_rank, int c_first, int pre_first) {
+                                                     const float4 *s_rank, int c_first, int pre_first, MhLeft lf,
+                                                     int left /* LEFT: the leftover items, which this wave evaluates (mh_left_batch) */) {
     constexpr int KN = KA > 0 ? KA : 1;   // a wave without items (KA == 0) only helps to stage the lists
     constexpr int KM = KA;
     const int V = vw.V;
@@ -688,23 +818,27 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         }
     };
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // list length of view vb + lane (0: the view does not see the point) and the inclusive prefix sum of the lists' records over
+    // the lanes: the first block's were made in the kernel's prologue, which requested the lengths and staged that block's
+    // first batch in front of its barrier (they are this loop's c and pre from the start: no registers of their own)
+    int c = c_first, pre = pre_first;
     for (int vb = 0; vb < V; vb += 64) {
-        const int vv = vb + lane;
-        // list length of view vv (0: the view does not see the point); the first block's was requested in the kernel's
-        // prologue, in front of the first barrier
-        const int c = vb == 0 ? c_first : ((vv < V) ? (int)vcnt[(size_t)vv * N + n] : 0);
-        const int len = mh_list_records<KEYS, BIGP>(c);
-        // inclusive prefix sum over the lanes (the first block's comes from the prologue, which staged that block's first
-        // batch in front of its barrier)
-        const int pre = vb == 0 ? pre_first : mh_wave_prefix_sum(len);
+        if (vb) {
+            const int vv = vb + lane;
+            c = (vv < V) ? (int)vcnt[(size_t)vv * N + n] : 0;
+            pre = mh_wave_prefix_sum(mh_list_records<KEYS, BIGP>(c));
+        }
         bool staged = vb == 0;
         unsigned long long todo = __ballot(c != 0);
         int base = 0;
+        if constexpr (LEFT) {
+            if (left && lane == 0) lf.vis[vb >> 6] = todo;
+        }
         while (todo) {
             // the next lists that fit together (pre is monotone: a prefix of the views left; one list always fits)
             const unsigned long long take = todo & __ballot(pre - base <= MH_S3_CAP);
             if (!staged) {
-                mh_stage_batch<T, KEYS>(taps, s_taps, vb, n, N, P1, c, len, pre, base, take, lane, wave);
+                mh_stage_batch<T, KEYS, BIGP>(taps, s_taps, vb, n, N, P1, c, pre, base, take, wave);
                 __syncthreads();   // (waits for the copies: they count on vmcnt, and the barrier's fence drains it)
             }
             staged = false;
@@ -714,10 +848,14 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                     const int b = (int)__builtin_ctzll(m);
                     m &= m - 1;
                     flush_upto(vb + b);
-                    const int L = __builtin_amdgcn_readlane(len, b);
+                    const int cb = __builtin_amdgcn_readlane(c, b);   // (the list's records from its taps, on the scalar side:
+                    const int L = mh_list_records<KEYS, BIGP>(cb);    // len is not a register of the tap loops)
                     const int off = __builtin_amdgcn_readlane(pre, b) - L - base;
-                    one_view(vb + b, s_taps + off, KEYS ? __builtin_amdgcn_readlane(c, b) : L - 1);
+                    one_view(vb + b, s_taps + off, cb);
                 }
+            }
+            if constexpr (LEFT) {   // 
+                if (left) mh_left_batch(vw.cams, Hf, Wf, V, offs, S, s_rank, s_taps, lf, nact, left, vb, c, mh_list_records<KEYS, BIGP>(c), pre, base, take);
             }
             __syncthreads();
             base = __builtin_amdgcn_readlane(pre, 63 - (int)__builtin_clzll(take));
@@ -737,6 +875,9 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                 s_loss[it] = nm / dn;
             }
         }
+    }
+    if constexpr (LEFT) {
+        if (left) mh_left_sums(lf, V, nact, left, thr, s_loss, s_pos);
     }
 }
 
@@ -763,6 +904,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     __shared__ float4 s_rank[MH_MAX_RANKS * 4];   // mh_sample_rank's record of every base-view rank
     __shared__ float s_bval[MH_MAX_RANKS];        // base_view_conf of the ranks
     __shared__ int s_tail;                        // first trailing sample of this point (mh_tail_from); S = none
+    __shared__ float2 s_left[BIGV ? 1 : MH_S3_LEFT_PAIRS];   // the leftover items' terms (MhLeft)
+    __shared__ unsigned s_lview[BIGV ? 1 : 64];
+    __shared__ unsigned long long s_lvis[BIGV ? 1 : 4];
 
     // Wave priority: everything that is not the tap loop -- prologue, staging, the per-view projection, the epilogue -- runs
     // at priority 1, the tap loop at 0.  The tap loops saturate the VALU whatever the arbiter picks; the other phases are
@@ -781,8 +925,8 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     // in flight while the rank records are made, and the barrier behind those waits for both
     const int len_first = mh_list_records<KEYS, BIGP>(c_first);
     const int pre_first = mh_wave_prefix_sum(len_first);
-    mh_stage_batch<T, KEYS>(taps, s_taps, 0, n, N, P1, c_first, len_first, pre_first, 0,
-                            __ballot(c_first != 0) & __ballot(pre_first <= MH_S3_CAP), tid & 63,
+    mh_stage_batch<T, KEYS, BIGP>(taps, s_taps, 0, n, N, P1, c_first, pre_first, 0,
+                            __ballot(c_first != 0) & __ballot(pre_first <= MH_S3_CAP),
                             __builtin_amdgcn_readfirstlane(tid >> 6));
     if (tid == 64) s_tail = mh_tail_from(rule, n, S);
     if (tid < nrank) {
@@ -800,11 +944,22 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     for (int r = 1; r < nrank; ++r)
         if (s_bval[r] > 0.0f) nvalid = r + 1;
     const int nact = nvalid * S;
+    // the items behind the last full slice (mh_left_batch): not a slice of the wave they fall to but a job of the last wave
+    const int nrest = __builtin_amdgcn_readfirstlane(nact & 63);   // (nact comes out of LDS: uniform, but in a vector register)
+    const int nleft = (!BIGV && KEYS && nrest <= MH_S3_LEFT_MAX && nrest * vw.V <= MH_S3_LEFT_PAIRS) ? nrest : 0;
     const int wave0 = tid & ~63;   // first item of this wave in slice 0
     int ka = 0;
-    for (int j = 0; j < 4; ++j) ka += (j * T + wave0 < nact) ? 1 : 0;
-#define MH_S3_ARGS vw, offs, S, n, N, P1, thr, taps, vcnt, nact, tid, s_loss, s_pos, s_taps, s_rank, c_first, pre_first
-    if (ka == 4) mh_search_slices_lds<4, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
+    for (int j = 0; j < 4; ++j) ka += (j * T + wave0 < nact - nleft) ? 1 : 0;
+    const MhLeft lf{s_left, s_lview, s_lvis};
+#define MH_S3_ARGS vw, offs, S, n, N, P1, thr, taps, vcnt, nact, tid, s_loss, s_pos, s_taps, s_rank, c_first, pre_first, lf, nleft
+    if (!BIGV && wave0 == T - 64 && nleft) {   // the last wave, with the leftover items: it never has four slices
+        if constexpr (!BIGV) {
+            if (ka == 3) mh_search_slices_lds<3, T, BIGV, KEYS, BIGP, true>(MH_S3_ARGS);
+            else if (ka == 2) mh_search_slices_lds<2, T, BIGV, KEYS, BIGP, true>(MH_S3_ARGS);
+            else if (ka == 1) mh_search_slices_lds<1, T, BIGV, KEYS, BIGP, true>(MH_S3_ARGS);
+            else mh_search_slices_lds<0, T, BIGV, KEYS, BIGP, true>(MH_S3_ARGS);
+        }
+    } else if (ka == 4) mh_search_slices_lds<4, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
     else if (ka == 3) mh_search_slices_lds<3, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
     else if (ka == 2) mh_search_slices_lds<2, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
     else if (ka == 1) mh_search_slices_lds<1, T, BIGV, KEYS, BIGP>(MH_S3_ARGS);
