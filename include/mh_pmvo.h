@@ -62,7 +62,8 @@ int mh_ctx_set_view_u8(mh_ctx *ctx, int view, const float *cam_host, const float
                        const unsigned char *ori_u8, const unsigned char *conf_u8, const unsigned char *mask_u8,
                        const float *lut_host /*[256][4]*/, void *stream);
 
-/* The S depth offsets of PMVO.sample_next_3d_pos (PMVO.py:274-278), host pointer, S <= 256. */
+/* The S depth offsets of PMVO.sample_next_3d_pos (PMVO.py:274-278), host pointer, S <= 256 (MH_ERR_ARG beyond).  The search
+ * entry points below add a limit of their own on S: nrank * S <= 1024 items per point. */
 int mh_ctx_set_depth_offsets(mh_ctx *ctx, const float *offsets_host, int S);
 
 /* Host -> device copy of a points chunk on `stream` (PMVO.py:40, `torch.from_numpy(points).type(torch.float).to(device)`):
@@ -115,7 +116,14 @@ size_t mh_search_counts_offset(mh_ctx *ctx, int N, int patch);
  * the batch are the trailing columns of ATen's sums over the views (option "sum_block") -- see mh_ctx_set_option.  Base view
  * indices of ranks whose base_val is <= 0 may be anything (they are clamped; PMVO.py:64 never takes those ranks).
  * The scratch is opaque and must come from this library's own preparation calls: the search relies on the tap records being
- * unit vectors (|cos| <= 1 + 2^-14 in its integer-key body). */
+ * unit vectors (|cos| <= 1 + 2^-14 in its integer-key body).
+ *
+ * The ranks and samples a call takes: nrank >= 1, rank_step >= 1, (nrank - 1) * rank_step < MH_TOPK, and -- one workgroup
+ * holds the nrank * S (rank, sample) items of a point -- nrank <= 16 and nrank * S <= 1024 (the reference's 10 ranks leave
+ * S <= 102; 16 ranks S <= 64; S = 256 four ranks).  mh_search_forward, mh_search_prepared and mh_forward refuse anything
+ * else with MH_ERR_ARG and a text that names the limit, before they launch anything: no output is written.  (Order of the
+ * checks: state -- views, depth offsets -- first; in mh_search_forward / mh_search_prepared then the pointers, then these
+ * limits; mh_forward, once the depth offsets are set, reports these limits before its front end's pointer and patch checks.) */
 int mh_search_forward(mh_ctx *ctx, const float *points, int N, int patch, float conf_threshold, int nrank,
                       int rank_step, const float *vis, const float *ori, const float *pixf,
                       const float *ori_patch, const float *conf_patch, const int32_t *base_idx,
@@ -192,7 +200,8 @@ int mh_sample_next(mh_ctx *ctx, const float *points, const int32_t *base_view, c
 /* compute_reproject_ori / compute_points_prj_ori (PMVO.py:219-260): D [V,N,S,2] = pixel(sample) - pixel(point). */
 int mh_reproject_ori(mh_ctx *ctx, const float *points, const float *samples, int N, int S, float *D, void *stream);
 /* compute_prj_loss (PMVO.py:151-209) on materialised tensors: loss [N], index int64 [N], high_conf [N];
- * all_loss [N,S] (the per-sample losses after the positive / low-confidence rules) may be NULL. */
+ * all_loss [N,S] (the per-sample losses after the positive / low-confidence rules) may be NULL.  S <= 8187: a workgroup keeps
+ * two floats of LDS per sample next to 36 bytes of its own, 64 KiB in all (MH_ERR_ARG beyond). */
 int mh_prj_loss(mh_ctx *ctx, const float *D, const float *ori_patch, const float *conf_patch, const float *vis, int V,
                 int N, int S, int P, float conf_threshold, float *loss, long long *index, unsigned char *high_conf,
                 float *all_loss, void *stream);

@@ -165,7 +165,8 @@ extern "C" int mh_ctx_set_view_u8(mh_ctx *ctx, int view, const float *cam_host, 
 }
 
 extern "C" int mh_ctx_set_depth_offsets(mh_ctx *ctx, const float *offsets_host, int S) {
-    if (!ctx || !offsets_host || S < 1 || S > 256) return fail(MH_ERR_ARG, "mh_ctx_set_depth_offsets: bad arguments");
+    if (!ctx || !offsets_host || S < 1) return fail(MH_ERR_ARG, "mh_ctx_set_depth_offsets: bad arguments");
+    if (S > 256) return fail(MH_ERR_ARG, "mh_ctx_set_depth_offsets: S = %d exceeds the limit of 256 samples", S);
     MH_HIP(hipSetDevice(ctx->device));
     if (ctx->offs) (void)hipFree(ctx->offs);
     ctx->offs = nullptr;
@@ -311,6 +312,22 @@ extern "C" size_t mh_search_scratch_bytes(mh_ctx *ctx, int N, int patch) {
     return SearchScratch(ctx->V, N, patch, nullptr).bytes;
 }
 
+// The ranks a search call takes -- ranks 0, rank_step, ... of the MH_TOPK ranked views -- and what one workgroup of the search
+// holds (csrc/mh_launch.h): at most MH_MAX_RANKS ranks and MH_MAX_ITEMS = nrank * S items.  Checked by every entry point in
+// front of its first launch (mh_launch_search would answer a bare -1 behind the front end).
+static int search_limits(const mh_ctx *ctx, const char *what, int nrank, int rank_step) {
+    if (nrank < 1 || rank_step < 1 || ((long long)nrank - 1) * rank_step >= MH_TOPK)
+        return fail(MH_ERR_ARG, "%s: bad arguments: nrank = %d, rank_step = %d (nrank >= 1, rank_step >= 1 and "
+                                "(nrank - 1) * rank_step < %d, the ranked views: MH_TOPK)", what, nrank, rank_step, MH_TOPK);
+    if (nrank > MH_MAX_RANKS)
+        return fail(MH_ERR_ARG, "%s: nrank = %d exceeds the limit of %d base-view ranks (MH_MAX_RANKS)", what, nrank,
+                    MH_MAX_RANKS);
+    if ((long long)nrank * ctx->S > MH_MAX_ITEMS)
+        return fail(MH_ERR_ARG, "%s: nrank * S = %d * %d items exceed the limit of %d items per point (MH_MAX_ITEMS)", what,
+                    nrank, ctx->S, MH_MAX_ITEMS);
+    return MH_OK;
+}
+
 // What mh_search_forward puts in front of the search: the tap lists from gathered patches (mh_forward_prepare writes them
 // from the maps instead)
 struct SearchPrep {
@@ -331,9 +348,9 @@ static int search(mh_ctx *ctx, const char *what, const SearchPrep *prep, const f
     if (!ctx->offs) return fail(MH_ERR_STATE, "%s: depth offsets not set", what);
     if (N == 0) return MH_OK;
     if (!points || !ori || !base_idx || !base_val || !scratch || !line_ori || !min_loss || !high_conf || N < 0 ||
-        nrank < 1 || rank_step < 1 || (nrank - 1) * rank_step >= MH_TOPK ||
         (prep && (!prep->vis || !prep->pixf || !prep->ori_patch || !prep->conf_patch)))
         return fail(MH_ERR_ARG, "%s: bad arguments", what);
+    if (int rc = search_limits(ctx, what, nrank, rank_step)) return rc;
     if (prep && prep->scratch_bytes < mh_search_scratch_bytes(ctx, N, patch))
         return fail(MH_ERR_ARG, "%s: scratch too small (%zu < %zu)", what, prep->scratch_bytes,
                     mh_search_scratch_bytes(ctx, N, patch));
@@ -400,6 +417,9 @@ extern "C" int mh_forward(mh_ctx *ctx, const float *points, int N, int patch, fl
                           int32_t *base_idx, float *base_val, float *line_ori, float *min_loss, uint8_t *high_conf,
                           float *best_sample, int32_t *best_rank, int32_t *best_s, void *stream) {
     if (!ctx || !ctx->rec) return fail(MH_ERR_STATE, "mh_forward: views not set");
+    // the rank arguments, in front of the front end's launch (the search checks them again, behind it)
+    if (N > 0 && ctx->offs)
+        if (int rc = search_limits(ctx, "mh_forward", nrank, rank_step)) return rc;
     // with the default kernels the ranking kernel also writes the work classes of the search's launch order (it has the
     // point's ranking in its lanes): one launch less per iteration than the three separate calls
     const bool fuse_cls = ctx->search_variant == 0 && (ctx->topk_order & 255) == 0 && N > 1 && base_idx && base_val && vis &&
@@ -595,6 +615,9 @@ extern "C" int mh_prj_loss(mh_ctx *ctx, const float *D, const float *ori_patch, 
     if (N == 0) return MH_OK;
     if (!ctx || !D || !ori_patch || !conf_patch || !vis || !loss || V < 1 || V >= 4096 || N < 0 || S < 1 || P < 1)
         return fail(MH_ERR_ARG, "mh_prj_loss: bad arguments");
+    if (S > MH_PRJ_LOSS_MAX_S)
+        return fail(MH_ERR_ARG, "mh_prj_loss: S = %d exceeds the limit of %d samples (two floats of LDS each, 64 KiB)", S,
+                    MH_PRJ_LOSS_MAX_S);
     return launched(mh_launch_prj_loss(D, ori_patch, conf_patch, vis, V, N, S, P, conf_threshold, loss, index, high_conf,
                                        all_loss, ctx->sum_block, (hipStream_t)stream),
                     "mh_prj_loss");

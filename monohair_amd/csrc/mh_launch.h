@@ -24,7 +24,15 @@ struct MhViews {
 // of the counting kernel adds to copy blockIdx % COPIES): up to 670 points of a 5000-point chunk share one (rank, base view),
 // and that many atomics on ONE address drain in ~9 us.  The C API hands the array out of the search scratch.
 #define MH_GROUP_COPIES 16
-#define MH_GROUP_RANKS 16   // = MH_MAX_RANKS of the search
+// One workgroup of the search holds one point: its nrank * S (rank, sample) items share LDS arrays of these sizes.  The entry
+// points of capi.cpp refuse more items or ranks (MH_ERR_ARG) before their first launch; mh_launch_search answers -1.
+#define MH_MAX_ITEMS 1024
+#define MH_MAX_RANKS 16
+#define MH_GROUP_RANKS MH_MAX_RANKS
+// mh_prj_loss_kernel keeps 2 * S floats of dynamic LDS next to MH_PRJ_LOSS_STATIC_LDS bytes of static LDS (s_npos, s_bl[4],
+// s_bi[4]); without a raised dynamic-LDS attribute a workgroup's static + dynamic LDS may not exceed 64 KiB
+#define MH_PRJ_LOSS_STATIC_LDS 36
+#define MH_PRJ_LOSS_MAX_S ((65536 - MH_PRJ_LOSS_STATIC_LDS) / 8)   // 8187
 
 #define MH_DG_MAXR 48                 // radius limit: sigma <= 11.9 at truncate 4 (the reference uses 0.4 and 10: 2 and 40)
 struct MhDogWeights {                 // device-resident; w[s][j + r[s]] for j = -r[s] .. 0 (the symmetric half incl. the centre)

@@ -4,8 +4,7 @@
 #pragma once
 #include "mh_device.h"
 
-#define MH_MAX_ITEMS 1024
-#define MH_MAX_RANKS 16
+// (MH_MAX_ITEMS / MH_MAX_RANKS: mh_launch.h -- the C ABI refuses what exceeds them before anything is launched)
 
 // PMVO.sample_next_3d_pos for one item (pixel(unrounded) + 2*(ori_col, ori_row) -> ndc -> unproject), split at what the S
 // samples of one base-view rank have in common (the point's pixel in the base view, the shifted pixel in NDC, the two quotients

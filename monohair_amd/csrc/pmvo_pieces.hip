@@ -279,7 +279,9 @@ extern "C" int mh_launch_reproject(MhViews vw, const float *pts, const float *sa
 extern "C" int mh_launch_prj_loss(const float *D, const float *ori_patch, const float *conf_patch, const float *vis, int V,
                                   int N, int S, int P, float thr, float *loss, long long *index, uint8_t *hc,
                                   float *all_loss, int sum_block, hipStream_t st) {
-    if (S < 1 || S > 8192) return -1;
+    // static + dynamic LDS of a workgroup may not exceed 64 KiB unless the kernel's dynamic-LDS attribute is raised (it is not)
+    static_assert(MH_PRJ_LOSS_STATIC_LDS + 2 * sizeof(float) * MH_PRJ_LOSS_MAX_S <= 65536, "mh_prj_loss_kernel's LDS");
+    if (S < 1 || S > MH_PRJ_LOSS_MAX_S) return -1;
     const long long cols = (long long)N * S;
     hipLaunchKernelGGL(mh_prj_loss_kernel, dim3(N), dim3(256), (size_t)2 * S * sizeof(float), st, D, ori_patch,
                        conf_patch, vis, V, N, S, P, thr, loss, index, hc, all_loss,

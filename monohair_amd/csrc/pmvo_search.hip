@@ -1056,6 +1056,114 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(KEYS ? MH_S3_
     }
 }
 
+// A batch of ONE candidate in all (N == 1 and S == 1): the reference's tensors are [V, 1], and two of its steps take other forms
+// there (oracle/pmvo_oracle.c: batch_is_single, tail_from_of).  compute_reproject_ori projects the sample, like the point,
+// through the single-column sgemm (single: option reproject_rule 0), and the sums over the views are ATen's sums over a
+// contiguous innermost dimension, not outer sums (inner_sum: option sum_block > 0; mh_inner_sum_views, as in the refine
+// kernels).  mh_launch_search sends this shape here and the search kernels above never see it.  One wave: the usable ranks
+// one after the other, a view per lane with the portable kernel's tap walk, then every lane the same sums over the views.
+__global__ __launch_bounds__(64) void mh_search_one_column_kernel(MhViews vw, const float *__restrict__ offs, int nrank,
+                                                                  int rank_step, const float *__restrict__ pts, int P1, float thr,
+                                                                  const float *__restrict__ ori_c,
+                                                                  const int32_t *__restrict__ base_idx,
+                                                                  const float *__restrict__ base_val,
+                                                                  const float4 *__restrict__ taps,
+                                                                  const uint8_t *__restrict__ vcnt /* may be null */,
+                                                                  float *__restrict__ line_ori, float *__restrict__ min_loss,
+                                                                  uint8_t *__restrict__ high_conf, float *__restrict__ best_sample,
+                                                                  int32_t *__restrict__ best_rank, int32_t *__restrict__ best_s,
+                                                                  MhRule rule, int single, int inner_sum) {
+    extern __shared__ float s_term[];   // [2][V]: (loss x weight, weight) of every view
+    const int lane = threadIdx.x, V = vw.V;
+    const float Hf = (float)vw.H, Wf = (float)vw.W;
+    const float P0 = pts[0], P1x = pts[1], P2 = pts[2];
+    const bool all_nan = mh_point_pixel_not_finite(vw, P0, P1x, P2, 1, lane, 64);
+    float ml = 0.0f, B0 = 0.0f, B1 = 0.0f, B2 = 0.0f;
+    int br = 0, hc = 0;
+    for (int r = 0; r < nrank; ++r) {
+        if (r > 0 && !(base_val[r * rank_step] > 0.0f)) continue;   // (PMVO.py:64 never takes such a rank; uniform)
+        const int b = min(max(base_idx[r * rank_step], 0), V - 1);
+        const float2 oc = reinterpret_cast<const float2 *>(ori_c)[b];
+        float X0, X1, X2;
+        mh_sample_next(vw.cams + b * MH_CAM_STRIDE, P0, P1x, P2, oc.x, oc.y, Hf, Wf, offs[0], X0, X1, X2,
+                       mh_group_forms(rule, r, V, b, 1));
+        for (int v = lane; v < V; v += MH_WAVE) {
+            float tn = 0.0f, td = 0.0f;
+            const float4 *__restrict__ rec = taps + (size_t)v * P1;
+            const float4 hdr = rec[0];
+            const int ntap = vcnt ? (int)vcnt[v] : __float_as_int(hdr.x);
+            if (ntap != 0 && hdr.y != -1.0f) {
+                float row, col, dx, dy;
+                mh_pixel_of_b(vw.cams + v * MH_CAM_STRIDE, X0, X1, X2, Hf, Wf, row, col, single != 0);
+                mh_unit2(row - hdr.z, col - hdr.w, dx, dy);
+                const float4 t0 = rec[1];
+                float l0 = 1.0f - __builtin_fabsf(t0.x * dx + t0.y * dy), bc = t0.z;
+                for (int t = 1; t < ntap; ++t) {
+                    const float4 tp = rec[1 + t];
+                    const float l = 1.0f - __builtin_fabsf(tp.x * dx + tp.y * dy);
+                    const bool upd = l < l0;
+                    l0 = upd ? l : l0;
+                    bc = upd ? tp.z : bc;
+                }
+                tn = l0 * bc;
+                td = bc;
+            }
+            s_term[v] = tn;
+            s_term[V + v] = td;
+        }
+        __syncthreads();
+        int cnt = 0;
+        for (int v = 0; v < V; ++v) cnt += (s_term[V + v] > 0.0f) ? 1 : 0;
+        float nm, dn;
+        if (inner_sum) {
+            nm = mh_inner_sum_views(V, [&](int v) { return s_term[v]; });
+            dn = mh_inner_sum_views(V, [&](int v) { return s_term[V + v]; });
+        } else {   // the cascade of the outer sums, as the search kernels add the views
+            MhCascV num = {0.0f, 0.0f, 0.0f}, den = {0.0f, 0.0f, 0.0f};
+            for (int v = 0; v < V; ++v) {
+                if (v > 0 && (v & 15) == 0) {
+                    mh_cascv_flush(num, v);
+                    mh_cascv_flush(den, v);
+                }
+                num.a0 = num.a0 + s_term[v];
+                den.a0 = den.a0 + s_term[V + v];
+            }
+            nm = mh_cascv_done(num);
+            dn = mh_cascv_done(den);
+        }
+        __syncthreads();
+        // one sample: fewer than five positive ones, the low-confidence rule keeps its loss (PMVO.py:199-206)
+        const float l = all_nan ? __builtin_nanf("") : nm / dn;
+        if (r == 0 || l < ml) {
+            ml = l;
+            br = r;
+            hc = (dn / (float)cnt > thr) ? 1 : 0;
+            B0 = X0;
+            B1 = X1;
+            B2 = X2;
+        }
+    }
+    if (lane == 0) {
+        const float d0 = B0 - P0, d1 = B1 - P1x, d2 = B2 - P2;
+        float s2 = d0 * d0;
+        s2 = mh_fma(d1, d1, s2);
+        s2 = mh_fma(d2, d2, s2);
+        const float nrm = __builtin_sqrtf(s2);
+        line_ori[0] = d0 / nrm;
+        line_ori[1] = d1 / nrm;
+        line_ori[2] = d2 / nrm;
+        min_loss[0] = ml;
+        high_conf[0] = (uint8_t)hc;
+        if (best_sample) {
+            best_sample[0] = B0;
+            best_sample[1] = B1;
+            best_sample[2] = B2;
+        }
+        if (best_rank) best_rank[0] = br;
+        if (best_s) best_s[0] = 0;
+    }
+}
+
 // Launch order of the search: points sorted by descending work = (taps of the views that see the point) x (item slices
 // it needs).  mh_search_work_kernel: one lane per point -> work class (0 = heaviest) in order[0..N);
 // mh_search_order_kernel: one workgroup -- histogram of the MH_ORDER_BUCKETS classes, exclusive scan, scatter of the
@@ -1152,6 +1260,13 @@ extern "C" int mh_launch_search(MhViews vw, const float *offs, int S, int nrank,
         if (hipMemsetAsync(gcnt, 0, sizeof(int32_t) * (size_t)MH_GROUP_COPIES * MH_GROUP_RANKS * vw.V, st) != hipSuccess) return -1;
         hipLaunchKernelGGL(mh_group_sizes_kernel, dim3((N + 255) / 256, nrank), dim3(256), sizeof(int) * (size_t)vw.V, st,
                            base_idx, N, vw.V, rank_step, gcnt);
+    }
+    // a batch of one candidate in all: its own forms (mh_search_one_column_kernel)
+    if ((long long)N * S == 1 && (rule_mode == 0 || sum_block > 0) && plan.part != MhSearchPlan::PART_PRE_ONLY) {
+        hipLaunchKernelGGL(mh_search_one_column_kernel, dim3(1), dim3(64), 2 * sizeof(float) * (size_t)vw.V, st, vw, offs, nrank,
+                           rank_step, pts, P1, thr, ori_c, base_idx, base_val, taps, cnt, line_ori, min_loss, high_conf,
+                           best_sample, best_rank, best_s, rule, rule_mode == 0 ? 1 : 0, sum_block > 0 ? 1 : 0);
+        return (int)hipGetLastError();
     }
     if (!portable) {
         // the launch order: work classes into order[0..N) unless the caller wrote them, then the points by class into order[N..2N)

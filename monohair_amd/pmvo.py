@@ -146,12 +146,19 @@ class PMVO:
         h = ctypes.c_void_p()
         _lib.check(self._L.mh_ctx_create(self.device.index or 0, ctypes.byref(h)), "mh_ctx_create")
         self._ctx = h
-        offs = depth_offsets(self.NUM_SAMPLE)
-        _lib.check(self._L.mh_ctx_set_depth_offsets(self._ctx, offs.ctypes.data_as(ctypes.c_void_p), len(offs)),
-                   "mh_ctx_set_depth_offsets")
+        self.set_num_sample(self.NUM_SAMPLE)
         self._scratch = None
         self.bust_tree = self.scalp_tree = self.scalp_max = None
         self.base_view_override = None
+
+    def set_num_sample(self, num_sample):
+        """The sample count of forward()'s search (the reference's default argument of sample_next_3d_pos, PMVO.py:263) on
+        this object: NUM_SAMPLE and the context's depth offsets.  The search takes up to 256 samples and, with the len(RANKS)
+        base-view ranks, up to 1024 (rank, sample) items (include/mh_pmvo.h)."""
+        offs = depth_offsets(int(num_sample))
+        _lib.check(self._L.mh_ctx_set_depth_offsets(self._ctx, offs.ctypes.data_as(ctypes.c_void_p), len(offs)),
+                   "mh_ctx_set_depth_offsets")
+        self.NUM_SAMPLE = len(offs)
 
     def _alloc(self, V, H, W):
         self.num_view = V
@@ -553,7 +560,7 @@ class PMVO:
         cnt = buf[off:off + self.num_view * N].view(self.num_view, N).to(torch.int64)
         nvalid = None
         if base_val is not None:
-            pos = base_val[list(self.RANKS)] > 0                      # [10, N]
+            pos = base_val[list(self.RANKS)] > 0                      # [len(RANKS), N]
             last = (pos * torch.arange(1, pos.shape[0] + 1, device=pos.device)[:, None]).amax(0)
             nvalid = torch.clamp(last, min=1)
         return cnt, nvalid
@@ -565,7 +572,9 @@ class PMVO:
         the tap preparation as separate kernels through the materialised patch tensors (same results).
         out=(line_ori [N,3] float32, min_loss [N] float32, high_conf [N] bool): contiguous device tensors the search
         writes into (the driver `optimize` passes slices of one result buffer: no per-chunk concatenation)."""
-        ranks = list(self.RANKS)
+        ranks = list(self.RANKS)          # (the class's, or a set installed on this object)
+        step = ranks[1] - ranks[0] if len(ranks) > 1 else 1
+        assert ranks == list(range(0, step * len(ranks), step)), "RANKS must be 0, step, 2 * step, ... (mh_forward's nrank, rank_step)"
         f = dict(dtype=torch.float32, device=self.device)
         cs = torch.cuda.current_stream(self.device)          # looked up once: ~8 us of Python per call
         stp = ctypes.c_void_p(cs.cuda_stream)
@@ -602,7 +611,7 @@ class PMVO:
             bval = torch.empty((20, N), **f)
             if N:
                 _lib.check(self._L.mh_forward(
-                    self._ctx, d_(points), N, self._side, float(self.conf_threshold), len(ranks), ranks[1] - ranks[0],
+                    self._ctx, d_(points), N, self._side, float(self.conf_threshold), len(ranks), step,
                     d_(self.visible), d_(self.Ori), d_(self.Conf), d_(self.mask), d_(scratch), need, d_(bidx32), d_(bval),
                     d_(line_ori), d_(min_loss), d_(hc), _lib.ptr(bs), _lib.ptr(br), _lib.ptr(bi), stp), "mh_forward")
         else:
@@ -619,13 +628,13 @@ class PMVO:
             if fused:
                 _lib.check(self._L.mh_search_prepared(
                     self._ctx, _lib.ptr(points), N, self._side, float(self.conf_threshold), len(ranks),
-                    ranks[1] - ranks[0], _lib.ptr(self.Ori), _lib.ptr(bidx32), _lib.ptr(bval), _lib.ptr(scratch),
+                    step, _lib.ptr(self.Ori), _lib.ptr(bidx32), _lib.ptr(bval), _lib.ptr(scratch),
                     _lib.ptr(line_ori), _lib.ptr(min_loss), _lib.ptr(hc), _lib.ptr(bs), _lib.ptr(br), _lib.ptr(bi),
                     stp), "mh_search_prepared")
             else:
                 _lib.check(self._L.mh_search_forward(
                     self._ctx, _lib.ptr(points), N, self._side, float(self.conf_threshold), len(ranks),
-                    ranks[1] - ranks[0], _lib.ptr(self.visible), _lib.ptr(self.Ori), _lib.ptr(self._pixf),
+                    step, _lib.ptr(self.visible), _lib.ptr(self.Ori), _lib.ptr(self._pixf),
                     _lib.ptr(self._Ori_patch), _lib.ptr(self._Conf_patch), _lib.ptr(bidx32), _lib.ptr(bval),
                     _lib.ptr(scratch), need, _lib.ptr(line_ori), _lib.ptr(min_loss), _lib.ptr(hc), _lib.ptr(bs),
                     _lib.ptr(br), _lib.ptr(bi), stp), "mh_search_forward")

@@ -120,12 +120,25 @@ class Scene:
         return PMVO.from_planes(self.rec, t(self.depth), t(self.ori), t(self.conf), t(self.mask), camera=self.cams, **kw)
 
 
-def run(scene, offsets, expect=None, runs=((0, 0), (1, 0), (2, 0), (0, 1256)), pts=None):
+def run(scene, offsets, expect=None, runs=((0, 0), (1, 0), (2, 0), (0, 1256)), pts=None, ranks=None, num_sample=None, info=None):
     """forward() with (search_body, search_variant) = default, key body, select body, portable kernel against oracle.forward;
-    expect = {(v, n): list length}.  Returns the [V, N] list lengths of the front end."""
+    expect = {(v, n): list length}.  Returns the [V, N] list lengths of the front end.  ranks: another set of base-view ranks
+    (PMVO.RANKS of the context, nrank / rank_step of the oracle); num_sample: another sample count (the context's and the
+    oracle's offsets become depth_offsets(num_sample)); info: a dict that receives the usable ranks per point the context
+    reports (search_work) and the oracle's winners."""
     pts = scene.pts if pts is None else pts
     pm = scene.context()
-    _, o_ori, o_loss, o_hc, o_ex = oracle.forward(scene.views(), pts, scene.patch, THR, offsets, extra=True)
+    okw = {}
+    if num_sample is not None:
+        from monohair_amd.pmvo import depth_offsets
+
+        offsets = depth_offsets(num_sample)
+        assert len(offsets) == num_sample
+        pm.set_num_sample(num_sample)
+    if ranks is not None:
+        pm.RANKS = ranks
+        okw = dict(nrank=len(ranks), rank_step=ranks[1] - ranks[0] if len(ranks) > 1 else 1)
+    _, o_ori, o_loss, o_hc, o_ex = oracle.forward(scene.views(), pts, scene.patch, THR, offsets, extra=True, **okw)
     ref = (o_ori, o_loss, o_hc, o_ex["best_s"], o_ex["best_rank"])
     cnt = None
     try:
@@ -135,10 +148,14 @@ def run(scene, offsets, expect=None, runs=((0, 0), (1, 0), (2, 0), (0, 1256)), p
             _, ori, loss, hc, ex = pm.forward(pts, extras=True)
             got = tuple(x.cpu().numpy() for x in (ori, loss, hc, ex["best_s"], ex["best_rank"]))
             if cnt is None:
-                cnt = pm.search_work(len(pts))[0].cpu().numpy()
+                cnt, nvalid = pm.search_work(len(pts), ex["base_val"])
+                cnt = cnt.cpu().numpy()
+                if info is not None:
+                    info.update(nvalid=nvalid.cpu().numpy(), best_s=o_ex["best_s"], best_rank=o_ex["best_rank"])
                 for (v, n), c in (expect or {}).items():
                     assert cnt[v, n] == c, (v, n, c, int(cnt[v, n]))
             for a, b in zip(got, ref):
+                assert a.shape == b.shape and len(a) == len(pts)
                 assert np.array_equal(a, b, equal_nan=(a.dtype.kind == "f")), (body, variant)
     finally:
         pm.set_option("search_body", 0)
