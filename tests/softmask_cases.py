@@ -384,10 +384,11 @@ def eligible_taps(t, thr):
 SEARCH_RULES = ("cmax", "tap", "weight")      # cmax > thr (:162), conf_p > thr (:178), sum(weight) / sum(weight > 0) > thr (:198)
 
 
-def prj_loss_np(D, op, cp, vis, thr, flip=None):
+def prj_loss_np(D, op, cp, vis, thr, flip=None, low_below=5):
     """compute_prj_loss in numpy float32 on D [V,N,S,2], Ori_patch [V,N,P,2], Conf_patch [V,N,P], visible [V,N], the sums over
-    the views in ATen's order; flip = one of SEARCH_RULES to evaluate with `>=` -> dict(loss, idx, hc [N], npos [N] = positive
-    samples, ratio [N,S] = sum(weight) / sum(weight > 0))"""
+    the views in ATen's order; flip = one of SEARCH_RULES to evaluate with `>=`; low_below = the bound of the low-confidence rule
+    (PMVO.py:199: 5) -> dict(loss, idx, hc [N], npos [N] = positive samples, ratio [N,S] = sum(weight) / sum(weight > 0),
+    all [N,S] = the losses the minimum is taken of)"""
     o = {k: OPS[">=" if k == flip else ">"] for k in SEARCH_RULES}
     V, N, S, _ = D.shape
     thr = F(thr)
@@ -413,12 +414,12 @@ def prj_loss_np(D, op, cp, vis, thr, flip=None):
         pos = o["weight"](ratio, thr)
         loss = tot(ml * w) / sw
     l2 = np.where(pos, loss, F(1))
-    low = pos.sum(-1) < 5
+    low = pos.sum(-1) < low_below
     l2[low] = loss[low]
     nan = np.isnan(l2)
     idx = np.where(nan.any(-1), nan.argmax(-1), np.argmin(np.where(nan, np.inf, l2), -1))
     rows = np.arange(N)
-    return dict(loss=l2[rows, idx], idx=idx, hc=pos[rows, idx], npos=pos.sum(-1), ratio=ratio)
+    return dict(loss=l2[rows, idx], idx=idx, hc=pos[rows, idx], npos=pos.sum(-1), ratio=ratio, all=l2)
 
 
 def search_sensitivity(D, op, cp, vis, thr, ref_idx, ref_hc):
