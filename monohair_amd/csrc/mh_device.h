@@ -337,6 +337,57 @@ __device__ __forceinline__ void mh_unit2_fast2(mh_v2f x0, mh_v2f x1, mh_v2f &o0,
     mh_div2x2(x0, x1, nrm, o0, o1);
 }
 
+// ---- one item: the twins of mh_div2x2 / mh_pixel_of_fast2 / mh_unit2_fast2 on plain registers -- the same operations in the
+// same order, element for element (mh_fma, the same reciprocal refinement, mh_sqrt_before_clamp), so the bits are the pair
+// form's.  For the odd item of a wave: as mh_splat() pairs both halves of every v_pk_* did the same work, and a v_pk_*_f32
+// issued alone costs about 1.8 ns against 1.0 to 1.1 ns of the plain operation (docs/HISTORY.md).
+__device__ __forceinline__ void mh_div1x2(float n0, float n1, float d, float &q0, float &q1) {
+    float r = __builtin_amdgcn_rcpf(d);
+    const float nd = -d;
+    const float e = mh_fma(nd, r, 1.0f);
+    r = mh_fma(e, r, r);
+    float a = n0 * r;
+    float ea = mh_fma(nd, a, n0);
+    a = mh_fma(ea, r, a);
+    ea = mh_fma(nd, a, n0);
+    q0 = mh_fma(ea, r, a);
+    float b = n1 * r;
+    float eb = mh_fma(nd, b, n1);
+    b = mh_fma(eb, r, b);
+    eb = mh_fma(nd, b, n1);
+    q1 = mh_fma(eb, r, b);
+}
+
+__device__ __forceinline__ void mh_pixel_of_fast1(const float *__restrict__ cam, float X0, float X1, float X2, float Hf,
+                                                  float Wf, float &row, float &col) {
+    float c0 = cam[0] * X0;
+    c0 = mh_fma(cam[1], X1, c0);
+    c0 = mh_fma(cam[2], X2, c0);
+    c0 = mh_fma(cam[3], 1.0f, c0);
+    float c1 = cam[4] * X0;
+    c1 = mh_fma(cam[5], X1, c1);
+    c1 = mh_fma(cam[6], X2, c1);
+    c1 = mh_fma(cam[7], 1.0f, c1);
+    float c2 = cam[8] * X0;
+    c2 = mh_fma(cam[9], X1, c2);
+    c2 = mh_fma(cam[10], X2, c2);
+    c2 = mh_fma(cam[11], 1.0f, c2);
+    const float q0 = mh_fma(cam[18], c2, cam[16] * c0);
+    const float q1 = mh_fma(cam[22], c2, cam[21] * c1);
+    float u, v;
+    mh_div1x2(q0, q1, c2, u, v);
+    col = (-u + 1.0f) * (Wf * 0.5f);
+    row = (v + 1.0f) * (Hf * 0.5f);
+}
+
+__device__ __forceinline__ void mh_unit2_fast1(float x0, float x1, float &o0, float &o1) {
+    float s = x0 * x0;
+    s = mh_fma(x1, x1, s);
+    float nrm = mh_sqrt_before_clamp(s);
+    nrm = (nrm < 1e-8f) ? 1e-8f : nrm;
+    mh_div1x2(x0, x1, nrm, o0, o1);
+}
+
 __device__ __forceinline__ float mh_clampf(float x, float lo, float hi) {
     return x < lo ? lo : (x > hi ? hi : x);
 }

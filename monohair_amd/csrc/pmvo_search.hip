@@ -402,6 +402,14 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
 //     go in several batches; the typical point (22 visible views x 46 taps) needs one.
 //   * the visible views, their list lengths and LDS offsets come from the compact [V,N] byte array of list lengths: one
 //     lane per view, a wave prefix sum, v_readlane -- no per-view header load, no branch on it.
+// How the items are dealt to the waves: 256 lanes x up to 4 item slots, slice j of wave w = the items from j * 256 + w * 64, so
+// 900 items (14 slices + 4 leftover items) are 4, 4, 3, 3 slices.  A wave projects its items two at a time per view
+// (mh_pixel_of_fast2: v_pk_*_f32, the pair's divisions share their instructions); the ODD item of a 3- or 1-slice wave goes
+// through the one-item twins (mh_pixel_of_fast1 / mh_unit2_fast1, the same operations on plain registers: the same bits) -- as
+// a pair of two equal halves it cost +3.3 % of the headline and +4 % on 8-bit maps (profiles/search_five_waves.txt).  The
+// two 3-slice waves still end every staging batch a quarter early; a workgroup of 320 lanes x 3 slots (five waves of 3, 3, 3,
+// 3, 2) was built against that and LOST 17 % (same file): five waves do not spread evenly over a CU's four SIMDs, and the
+// kernel runs at the pace of the fullest SIMD.
 // ---------------------------------------------------------------------------------------------
 #define MH_S3_GRP 4      // tap records per ping-pong group
 #ifndef MH_S3_WAVES
@@ -671,12 +679,10 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
             DY[2 * jp] = dy.x;
             DY[2 * jp + 1] = dy.y;
         }
-        if constexpr (KA & 1) {
-            mh_v2f row, col, dx, dy;
-            mh_pixel_of_fast2(cam, mh_splat(X0[KA - 1]), mh_splat(X1[KA - 1]), mh_splat(X2[KA - 1]), Hf, Wf, row, col);
-            mh_unit2_fast2(row - mh_splat(hdr.z), col - mh_splat(hdr.w), dx, dy);
-            DX[KA - 1] = dx.x;
-            DY[KA - 1] = dy.x;
+        if constexpr (KA & 1) {   // the odd item: the one-item twins, not a pair of two equal halves (same bits: mh_device.h)
+            float row, col;
+            mh_pixel_of_fast1(cam, X0[KA - 1], X1[KA - 1], X2[KA - 1], Hf, Wf, row, col);
+            mh_unit2_fast1(row - hdr.z, col - hdr.w, DX[KA - 1], DY[KA - 1]);
         }
         constexpr int GRP = MH_S3_GRP;
         // the compare-and-select body: exact everywhere (the one body of rounds 1-3; with KEYS the re-evaluation path)
