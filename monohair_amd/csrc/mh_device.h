@@ -339,8 +339,9 @@ __device__ __forceinline__ void mh_unit2_fast2(mh_v2f x0, mh_v2f x1, mh_v2f &o0,
 
 // ---- one item: the twins of mh_div2x2 / mh_pixel_of_fast2 / mh_unit2_fast2 on plain registers -- the same operations in the
 // same order, element for element (mh_fma, the same reciprocal refinement, mh_sqrt_before_clamp), so the bits are the pair
-// form's.  For the odd item of a wave: as mh_splat() pairs both halves of every v_pk_* did the same work, and a v_pk_*_f32
-// issued alone costs about 1.8 ns against 1.0 to 1.1 ns of the plain operation (docs/HISTORY.md).
+// form's.  For every item of the search's key kernels and for the odd item of a wave of its select-only kernel (pmvo_search.hip,
+// above mh_search3_kernel): as mh_splat() pairs both halves of every v_pk_* did the same work, and a v_pk_*_f32 issued alone
+// costs about 1.8 ns against 1.0 to 1.1 ns of the plain operation (docs/HISTORY.md).
 __device__ __forceinline__ void mh_div1x2(float n0, float n1, float d, float &q0, float &q1) {
     float r = __builtin_amdgcn_rcpf(d);
     const float nd = -d;

@@ -403,13 +403,19 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
 //   * the visible views, their list lengths and LDS offsets come from the compact [V,N] byte array of list lengths: one
 //     lane per view, a wave prefix sum, v_readlane -- no per-view header load, no branch on it.
 // How the items are dealt to the waves: 256 lanes x up to 4 item slots, slice j of wave w = the items from j * 256 + w * 64, so
-// 900 items (14 slices + 4 leftover items) are 4, 4, 3, 3 slices.  A wave projects its items two at a time per view
-// (mh_pixel_of_fast2: v_pk_*_f32, the pair's divisions share their instructions); the ODD item of a 3- or 1-slice wave goes
-// through the one-item twins (mh_pixel_of_fast1 / mh_unit2_fast1, the same operations on plain registers: the same bits) -- as
-// a pair of two equal halves it cost +3.3 % of the headline and +4 % on 8-bit maps (profiles/search_five_waves.txt).  The
-// two 3-slice waves still end every staging batch a quarter early; a workgroup of 320 lanes x 3 slots (five waves of 3, 3, 3,
-// 3, 2) was built against that and LOST 17 % (same file): five waves do not spread evenly over a CU's four SIMDs, and the
-// kernel runs at the pace of the fullest SIMD.
+// 900 items (14 slices + 4 leftover items) are 4, 4, 3, 3 slices.  How a wave projects its items per view depends on what runs
+// beside it (profiles/search_projection_plain.txt; this file is built with -fno-slp-vectorize, or the compiler packs the plain
+// chains again and spills).  The KEY kernels project every item through the one-item forms (mh_pixel_of_fast1 / mh_unit2_fast1:
+// plain registers, no v_pk_*_f32 anywhere in them): a projecting wave there shares its SIMD with waves in their key blocks, and
+// beside those the packed chain of four items costs the SIMD 1103 cycles where four plain chains cost 819 (tools/ubench/
+// proj_forms.hip) -- +0.8 % on the headline.  The SELECT-ONLY kernel (8-bit contexts: lists of 2.5 taps, three quarters of it
+// projection) keeps the items two at a time (mh_pixel_of_fast2: v_pk_*_f32, the pair's divisions share their instructions) and
+// only the ODD item of a 3- or 1-slice wave on the one-item twins: its waves project beside waves that project, where the packed
+// form is the cheaper one (483 against 579 cycles); all items plain cost it 4 % (same file).  Both forms are the same operations
+// in the same order: the same bits.
+// The two 3-slice waves still end every staging batch a quarter early; a workgroup of 320 lanes x 3 slots (five waves of 3, 3,
+// 3, 3, 2) was built against that and LOST 17 % (profiles/search_five_waves.txt): five waves do not spread evenly over a CU's
+// four SIMDs, and the kernel runs at the pace of the fullest SIMD.
 // ---------------------------------------------------------------------------------------------
 #define MH_S3_GRP 4      // tap records per ping-pong group
 #ifndef MH_S3_WAVES
@@ -668,21 +674,33 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         const float4 hdr = rec[0];
         const float4 t0 = rec[1];
         float DX[KN], DY[KN], ML[KN], BC[KN];
+        if constexpr (KEYS) {
+            // beside waves that are in a key block every item goes through the one-item forms (plain registers, no v_pk_*_f32:
+            // this file is built without SLP packing); see the comment above mh_search3_kernel
 #pragma unroll
-        for (int jp = 0; jp < KA / 2; ++jp) {
-            mh_v2f row, col, dx, dy;
-            mh_pixel_of_fast2(cam, mh_v2f{X0[2 * jp], X0[2 * jp + 1]}, mh_v2f{X1[2 * jp], X1[2 * jp + 1]},
-                              mh_v2f{X2[2 * jp], X2[2 * jp + 1]}, Hf, Wf, row, col);
-            mh_unit2_fast2(row - mh_splat(hdr.z), col - mh_splat(hdr.w), dx, dy);
-            DX[2 * jp] = dx.x;
-            DX[2 * jp + 1] = dx.y;
-            DY[2 * jp] = dy.x;
-            DY[2 * jp + 1] = dy.y;
-        }
-        if constexpr (KA & 1) {   // the odd item: the one-item twins, not a pair of two equal halves (same bits: mh_device.h)
-            float row, col;
-            mh_pixel_of_fast1(cam, X0[KA - 1], X1[KA - 1], X2[KA - 1], Hf, Wf, row, col);
-            mh_unit2_fast1(row - hdr.z, col - hdr.w, DX[KA - 1], DY[KA - 1]);
+            for (int j = 0; j < KA; ++j) {
+                float row, col;
+                mh_pixel_of_fast1(cam, X0[j], X1[j], X2[j], Hf, Wf, row, col);
+                mh_unit2_fast1(row - hdr.z, col - hdr.w, DX[j], DY[j]);
+            }
+        } else {
+            // the select-only kernel: two items at a time on register pairs, the odd item through the one-item twins
+#pragma unroll
+            for (int jp = 0; jp < KA / 2; ++jp) {
+                mh_v2f row, col, dx, dy;
+                mh_pixel_of_fast2(cam, mh_v2f{X0[2 * jp], X0[2 * jp + 1]}, mh_v2f{X1[2 * jp], X1[2 * jp + 1]},
+                                  mh_v2f{X2[2 * jp], X2[2 * jp + 1]}, Hf, Wf, row, col);
+                mh_unit2_fast2(row - mh_splat(hdr.z), col - mh_splat(hdr.w), dx, dy);
+                DX[2 * jp] = dx.x;
+                DX[2 * jp + 1] = dx.y;
+                DY[2 * jp] = dy.x;
+                DY[2 * jp + 1] = dy.y;
+            }
+            if constexpr (KA & 1) {
+                float row, col;
+                mh_pixel_of_fast1(cam, X0[KA - 1], X1[KA - 1], X2[KA - 1], Hf, Wf, row, col);
+                mh_unit2_fast1(row - hdr.z, col - hdr.w, DX[KA - 1], DY[KA - 1]);
+            }
         }
         constexpr int GRP = MH_S3_GRP;
         // the compare-and-select body: exact everywhere (the one body of rounds 1-3; with KEYS the re-evaluation path)

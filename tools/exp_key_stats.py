@@ -19,6 +19,7 @@ def build():
     objs = [o for o in sorted(os.listdir(CSRC)) if o.endswith(".o") and o != "pmvo_search.o"]
     so = os.path.join(CSRC, "pmvo_search_keystats.o")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                           "-fno-slp-vectorize",       # (as csrc/Makefile builds this file)
                            "-DMH_KEY_STATS", "-c", os.path.join(CSRC, "pmvo_search.hip"), "-o", so])
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, so] +
                           [os.path.join(CSRC, o) for o in objs if o != "pmvo_search_keystats.o"] + ["-ldl"])
