@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/mh_pmvo.h"   // MH_CAM_STRIDE, MH_TOPK
 
 struct MhViews {
@@ -90,6 +92,19 @@ struct MhSearchPlan {
         PART_KERNEL_ONLY    // mh_search3_kernel alone on what PART_PRE_ONLY left in the scratch (10)
     } part;
 };
+
+// The patch sides the kernels templated on PATCH are built for: odd sides 1..11 (the reference's configurations use 5, 7 and
+// 9).  launch(std::integral_constant<int, PATCH>) launches the instantiation(s) of a launcher; the answer is what they left in
+// hipGetLastError, or -1 -- nothing launched -- for any other side (the C API turns that into MH_ERR_ARG).
+template <int... PS, typename F>
+static inline int mh_dispatch_patch_among(int patch, F &&launch) {
+    const bool launched = ((patch == PS && (launch(std::integral_constant<int, PS>{}), true)) || ...);
+    return launched ? (int)hipGetLastError() : -1;
+}
+template <typename F>
+static inline int mh_dispatch_patch(int patch, F &&launch) {
+    return mh_dispatch_patch_among<1, 3, 5, 7, 9, 11>(patch, launch);
+}
 
 extern "C" {
 // ---- pmvo_project.hip

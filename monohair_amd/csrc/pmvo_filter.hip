@@ -6,7 +6,7 @@
 // One wave per point, lane = view.  Each lane writes its per-view terms to LDS and lane 0 adds them in
 // ATen's cascade order (mask values in (0, 0.2] stay fractional, PMVO.py:427, so order can matter) -- in its row_sum
 // order for the trailing points of a batch of the reference (MhBatch).
-#include "mh_device.h"
+#include "mh_front.h"
 
 #define MH_FILTER_VMAX 512
 #define MH_NTERM 8
@@ -18,14 +18,76 @@ struct MhTailRows {
     int per_batch, count;
 };
 
+// The eight terms of one (point, view) that the votes sum over the views, from what its centre sample gave: the depth gap
+// against the four thresholds, the soft mask value m and the patch's confidence maximum cmax.  put(t, value) takes term t.
+template <typename Put>
+__device__ __forceinline__ void mh_vote_terms_of(bool oob, float gap, float cmax, float m, float thr, float vis_thr, Put &&put) {
+    const float unv = (oob || gap > 0.1f) ? 1.0f : 0.0f;
+    const float unv1 = (oob || gap > vis_thr) ? 1.0f : 0.0f;
+    const float unv9 = (oob || gap > 0.9f) ? 1.0f : 0.0f;
+    const float unvh = (gap >= vis_thr) ? 1.0f : 0.0f;   // filter_head_points: '>=' and no oob override
+    const float lowc = (cmax < thr) ? 1.0f : 0.0f;
+    m = (m > 0.2f) ? 1.0f : m;                           // the soft mask: values in (0, 0.2] stay fractional (PMVO.py:427)
+    const float visb = 1.0f - unv, visb1 = 1.0f - unv1, visbh = 1.0f - unvh;
+    put(0, visb * lowc);    // visible with low confidence
+    put(1, visb);           // visibles
+    put(2, visb * m);       // visibles * masks
+    put(3, visb1);          // visibles1
+    put(4, visb1 * m);      // visibles1 * masks
+    put(5, 1.0f - unv9);    // compute_unvisible_points
+    put(6, visbh);          // filter_head_points visibles
+    put(7, visbh * m);      // filter_head_points indexs
+}
+// ... and from the point itself: the centre sample of view v (mh_front.h), its record and mask value, and -- for term 0 alone,
+// so views that do not see the point skip it -- the maximum of the raw (unclamped) confidences of the patch (PMVO.py:415-420).
+template <int PATCH, typename Put>
+__device__ __forceinline__ void mh_vote_terms(const MhViews &vw, int v, float X0, float X1, float X2, bool single,
+                                              bool want_patch, float thr, float vis_thr, Put &&put) {
+    const int H = vw.H, W = vw.W;
+    const MhCentre s = mh_centre_sample(vw.cams + v * MH_CAM_STRIDE, X0, X1, X2, H, W, single);
+    const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
+    const float4 q = rec[(size_t)s.r * W + s.c];
+    const float m = vw.mask[(size_t)v * H * W + (size_t)s.r * W + s.c];
+    const float gap = mh_centre_gap(s, q);
+    float cmax = 0.0f;
+    if (want_patch && !(s.oob || gap > 0.1f)) {
+        // all PATCH*PATCH loads are issued before the first use (fully unrolled): the lane is latency bound
+        constexpr int HP = PATCH / 2;
+        float cv[PATCH * PATCH];
+#pragma unroll
+        for (int i = -HP; i <= HP; ++i)
+#pragma unroll
+            for (int j = -HP; j <= HP; ++j) cv[(i + HP) * PATCH + j + HP] = rec[mh_tap_pixel(s.r, s.c, i, j, H, W)].z;
+        cmax = q.z;
+#pragma unroll
+        for (int p = 0; p < PATCH * PATCH; ++p) cmax = (cv[p] > cmax) ? cv[p] : cmax;
+    }
+    mh_vote_terms_of(s.oob, gap, cmax, m, thr, vis_thr, put);
+}
+
+// the four decisions of a point from its eight sums over the views (PMVO.py:430-459, :476-480, :130-137)
+struct MhVotes {
+    bool surface, filter, unvisible, head;
+};
+__device__ __forceinline__ MhVotes mh_vote_decide(float s_idx, float s_vis, float s_vm, float s_vis1, float s_vm1, float s_v9,
+                                                  float s_vh, float s_ih) {
+    const bool low_conf = s_idx > 4.0f;
+    const bool hair = (s_vis - s_vm) < (s_vis * 1.0f / 2.0f);
+    const bool hair1 = (s_vis1 - s_vm1) < (s_vis1 * 1.0f / 2.0f);
+    const bool surf0 = s_vis > 1.0f;
+    const bool filt0 = (s_vis1 > 1.0f) && !surf0;
+    return {surf0 && !low_conf && hair, filt0 && !low_conf && hair1, !(s_v9 > 2.0f),
+            !((s_vh - s_ih) < (s_vh * 1.0f / 2.0f))};
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // mh_filter_rows_kernel (round 6): the same votes with lane = POINT.  mh_filter_kernel's wave is one point and its lanes
 // are 60 views -- 60 isolated 20-byte gathers in 60 different images per wave, each moving whole lines: 10.2 GB fetched
 // per pass for 0.68 GB of algorithmic bytes (profiles/r06_fullpass_summary.txt).  Here a wave is 64 CONSECUTIVE points
 // (neighbours in space: the candidates come in volume raster order) walking the views together: a wave's centre gathers
 // and patch rows of one view are neighbouring pixels of ONE image, every lane adds its own per-view terms in ATen's
-// cascade order in registers (no LDS, no serial lane-0 sum).  Per (point, view) the arithmetic is mh_filter_kernel's,
-// statement for statement.  Rows whose sums take another order (MhTailRows) are skipped here and done by mh_filter_kernel.
+// cascade order in registers (no LDS, no serial lane-0 sum).  Rows whose sums take another order (MhTailRows) are skipped
+// here and done by mh_filter_kernel.
 // ---------------------------------------------------------------------------------------------------------------
 template <int PATCH>
 __global__ __launch_bounds__(256) void mh_filter_rows_kernel(MhViews vw, const float *__restrict__ pts, int N, float thr,
@@ -34,7 +96,6 @@ __global__ __launch_bounds__(256) void mh_filter_rows_kernel(MhViews vw, const f
                                                              uint8_t *__restrict__ unvisible_index,
                                                              uint8_t *__restrict__ head_filter, MhBatch bt,
                                                              const int32_t *__restrict__ order) {
-    constexpr int HP = PATCH / 2;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     // order (optional): the rows in an order that puts spatial neighbours into one wave (sorted by grid cell, mh_grid_build):
@@ -55,59 +116,33 @@ __global__ __launch_bounds__(256) void mh_filter_rows_kernel(MhViews vw, const f
 #pragma unroll
             for (int t = 0; t < MH_NTERM; ++t) mh_cascv_flush(acc[t], v);
         }
-        const float *cam = vw.cams + v * MH_CAM_STRIDE;
-        float u, w, z, rowf, colf;
-        mh_cam_project_b(cam, X0, X1, X2, u, w, z, single);
-        mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        int r, c;
-        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
+        // (the text of mh_vote_terms<PATCH>: with the patch maximum behind a call the compiler unrolls the view loop of sides 9
+        // and 11, and side 9 takes one VGPR more)
+        const MhCentre s = mh_centre_sample(vw.cams + v * MH_CAM_STRIDE, X0, X1, X2, H, W, single);
         const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
-        const float4 q = rec[(size_t)r * W + c];
-        float m = vw.mask[(size_t)v * H * W + (size_t)r * W + c];
-        const float gap = (-z / 2.0f) * 255.0f - q.w;
+        const float4 q = rec[(size_t)s.r * W + s.c];
+        const float m = vw.mask[(size_t)v * H * W + (size_t)s.r * W + s.c];
+        const float gap = mh_centre_gap(s, q);
         float cmax = 0.0f;
-        if (want_patch && !(oob || gap > 0.1f)) {
-            // all PATCH*PATCH loads are issued before the first use (fully unrolled): the lane is latency bound
+        if (want_patch && !(s.oob || gap > 0.1f)) {
+            constexpr int HP = PATCH / 2;
             float cv[PATCH * PATCH];
 #pragma unroll
             for (int i = -HP; i <= HP; ++i)
 #pragma unroll
-                for (int j = -HP; j <= HP; ++j) {
-                    const int rr2 = min(max(r + i, 0), H - 1), cc2 = min(max(c + j, 0), W - 1);
-                    cv[(i + HP) * PATCH + j + HP] = rec[(size_t)rr2 * W + cc2].z;
-                }
+                for (int j = -HP; j <= HP; ++j) cv[(i + HP) * PATCH + j + HP] = rec[mh_tap_pixel(s.r, s.c, i, j, H, W)].z;
             cmax = q.z;
 #pragma unroll
-            for (int t = 0; t < PATCH * PATCH; ++t) cmax = (cv[t] > cmax) ? cv[t] : cmax;
+            for (int p = 0; p < PATCH * PATCH; ++p) cmax = (cv[p] > cmax) ? cv[p] : cmax;
         }
-        const float unv = (oob || gap > 0.1f) ? 1.0f : 0.0f;
-        const float unv1 = (oob || gap > vis_thr) ? 1.0f : 0.0f;
-        const float unv9 = (oob || gap > 0.9f) ? 1.0f : 0.0f;
-        const float unvh = (gap >= vis_thr) ? 1.0f : 0.0f;   // filter_head_points: '>=' and no oob override
-        const float lowc = (cmax < thr) ? 1.0f : 0.0f;
-        m = (m > 0.2f) ? 1.0f : m;
-        const float visb = 1.0f - unv, visb1 = 1.0f - unv1, visbh = 1.0f - unvh;
-        acc[0].a0 = acc[0].a0 + visb * lowc;
-        acc[1].a0 = acc[1].a0 + visb;
-        acc[2].a0 = acc[2].a0 + visb * m;
-        acc[3].a0 = acc[3].a0 + visb1;
-        acc[4].a0 = acc[4].a0 + visb1 * m;
-        acc[5].a0 = acc[5].a0 + (1.0f - unv9);
-        acc[6].a0 = acc[6].a0 + visbh;
-        acc[7].a0 = acc[7].a0 + visbh * m;
+        mh_vote_terms_of(s.oob, gap, cmax, m, thr, vis_thr, [&](int t, float x) { acc[t].a0 = acc[t].a0 + x; });
     }
-    const float s_idx = mh_cascv_done(acc[0]), s_vis = mh_cascv_done(acc[1]), s_vm = mh_cascv_done(acc[2]);
-    const float s_vis1 = mh_cascv_done(acc[3]), s_vm1 = mh_cascv_done(acc[4]), s_v9 = mh_cascv_done(acc[5]);
-    const float s_vh = mh_cascv_done(acc[6]), s_ih = mh_cascv_done(acc[7]);
-    const bool low_conf = s_idx > 4.0f;
-    const bool hair = (s_vis - s_vm) < (s_vis * 1.0f / 2.0f);
-    const bool hair1 = (s_vis1 - s_vm1) < (s_vis1 * 1.0f / 2.0f);
-    const bool surf0 = s_vis > 1.0f;
-    const bool filt0 = (s_vis1 > 1.0f) && !surf0;
-    if (surface_index) surface_index[n] = (surf0 && !low_conf && hair) ? 1 : 0;
-    if (filter_index) filter_index[n] = (filt0 && !low_conf && hair1) ? 1 : 0;
-    if (unvisible_index) unvisible_index[n] = (s_v9 > 2.0f) ? 0 : 1;
-    if (head_filter) head_filter[n] = ((s_vh - s_ih) < (s_vh * 1.0f / 2.0f)) ? 0 : 1;
+    const MhVotes d = mh_vote_decide(mh_cascv_done(acc[0]), mh_cascv_done(acc[1]), mh_cascv_done(acc[2]), mh_cascv_done(acc[3]),
+                                     mh_cascv_done(acc[4]), mh_cascv_done(acc[5]), mh_cascv_done(acc[6]), mh_cascv_done(acc[7]));
+    if (surface_index) surface_index[n] = d.surface;
+    if (filter_index) filter_index[n] = d.filter;
+    if (unvisible_index) unvisible_index[n] = d.unvisible;
+    if (head_filter) head_filter[n] = d.head;
 }
 
 template <int PATCH>
@@ -116,7 +151,6 @@ __global__ __launch_bounds__(256) void mh_filter_kernel(MhViews vw, const float 
                                                         uint8_t *__restrict__ filter_index,
                                                         uint8_t *__restrict__ unvisible_index,
                                                         uint8_t *__restrict__ head_filter, MhBatch bt, MhTailRows tr) {
-    constexpr int HP = PATCH / 2;
     extern __shared__ float s_tbuf[];   // [4 waves][MH_NTERM][V]
 #define s_t(w, t, v) s_tbuf[((w) * MH_NTERM + (t)) * V + (v)]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -128,56 +162,15 @@ __global__ __launch_bounds__(256) void mh_filter_kernel(MhViews vw, const float 
         n = (int)(row - bt.row0);
     }
     if (n >= N) return;
-    const int V = vw.V, H = vw.H, W = vw.W;
+    const int V = vw.V;
     const float X0 = pts[3 * n], X1 = pts[3 * n + 1], X2 = pts[3 * n + 2];
     // a batch of ONE point: its [V,1] sums over the views are ATen's inner sums whenever the outer-sum rule is on (sum_block > 0)
     // and -- with the batch rule of the products (reproject_rule 0) -- its projections are single-column products
     const bool one_point = mh_batch_single(bt, n);
     const bool single = bt.single_ok && one_point;
     for (int v = lane; v < V; v += MH_WAVE) {
-        const float *cam = vw.cams + v * MH_CAM_STRIDE;
-        float u, w, z, rowf, colf;
-        mh_cam_project_b(cam, X0, X1, X2, u, w, z, single);
-        mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        int r, c;
-        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
-        const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
-        const float4 q = rec[(size_t)r * W + c];
-        float m = vw.mask[(size_t)v * H * W + (size_t)r * W + c];
-        const float gap = (-z / 2.0f) * 255.0f - q.w;
-        // raw (unclamped) patch confidences, zeroed when the point projects outside (PMVO.py:415-420)
-        // (only term 0 = visible * low_confidence uses it, so views that do not see the point skip the patch)
-        float cmax = 0.0f;
-        if ((surface_index || filter_index) && !(oob || gap > 0.1f)) {
-            // all PATCH*PATCH loads are issued before the first use (fully unrolled): the lane is latency bound
-            float cv[PATCH * PATCH];
-#pragma unroll
-            for (int i = -HP; i <= HP; ++i)
-#pragma unroll
-                for (int j = -HP; j <= HP; ++j) {
-                    const int rr2 = min(max(r + i, 0), H - 1), cc2 = min(max(c + j, 0), W - 1);
-                    cv[(i + HP) * PATCH + j + HP] = rec[(size_t)rr2 * W + cc2].z;
-                }
-            cmax = q.z;
-#pragma unroll
-            for (int t = 0; t < PATCH * PATCH; ++t) cmax = (cv[t] > cmax) ? cv[t] : cmax;
-            if (oob) cmax = 0.0f;
-        }
-        const float unv = (oob || gap > 0.1f) ? 1.0f : 0.0f;
-        const float unv1 = (oob || gap > vis_thr) ? 1.0f : 0.0f;
-        const float unv9 = (oob || gap > 0.9f) ? 1.0f : 0.0f;
-        const float unvh = (gap >= vis_thr) ? 1.0f : 0.0f;   // filter_head_points: '>=' and no oob override
-        const float lowc = (cmax < thr) ? 1.0f : 0.0f;
-        m = (m > 0.2f) ? 1.0f : m;
-        const float visb = 1.0f - unv, visb1 = 1.0f - unv1, visbh = 1.0f - unvh;
-        s_t(wave, 0, v) = visb * lowc;    // visible with low confidence
-        s_t(wave, 1, v) = visb;           // visibles
-        s_t(wave, 2, v) = visb * m;       // visibles * masks
-        s_t(wave, 3, v) = visb1;          // visibles1
-        s_t(wave, 4, v) = visb1 * m;      // visibles1 * masks
-        s_t(wave, 5, v) = 1.0f - unv9;    // compute_unvisible_points
-        s_t(wave, 6, v) = visbh;          // filter_head_points visibles
-        s_t(wave, 7, v) = visbh * m;      // filter_head_points indexs
+        mh_vote_terms<PATCH>(vw, v, X0, X1, X2, single, surface_index || filter_index, thr, vis_thr,
+                             [&](int t, float x) { s_t(wave, t, v) = x; });
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -196,18 +189,12 @@ __global__ __launch_bounds__(256) void mh_filter_kernel(MhViews vw, const float 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
-        const float s_idx = s_t(wave, 0, 0), s_vis = s_t(wave, 1, 0), s_vm = s_t(wave, 2, 0);
-        const float s_vis1 = s_t(wave, 3, 0), s_vm1 = s_t(wave, 4, 0), s_v9 = s_t(wave, 5, 0);
-        const float s_vh = s_t(wave, 6, 0), s_ih = s_t(wave, 7, 0);
-        const bool low_conf = s_idx > 4.0f;
-        const bool hair = (s_vis - s_vm) < (s_vis * 1.0f / 2.0f);
-        const bool hair1 = (s_vis1 - s_vm1) < (s_vis1 * 1.0f / 2.0f);
-        const bool surf0 = s_vis > 1.0f;
-        const bool filt0 = (s_vis1 > 1.0f) && !surf0;
-        if (surface_index) surface_index[n] = (surf0 && !low_conf && hair) ? 1 : 0;
-        if (filter_index) filter_index[n] = (filt0 && !low_conf && hair1) ? 1 : 0;
-        if (unvisible_index) unvisible_index[n] = (s_v9 > 2.0f) ? 0 : 1;
-        if (head_filter) head_filter[n] = ((s_vh - s_ih) < (s_vh * 1.0f / 2.0f)) ? 0 : 1;
+        const MhVotes d = mh_vote_decide(s_t(wave, 0, 0), s_t(wave, 1, 0), s_t(wave, 2, 0), s_t(wave, 3, 0), s_t(wave, 4, 0),
+                                         s_t(wave, 5, 0), s_t(wave, 6, 0), s_t(wave, 7, 0));
+        if (surface_index) surface_index[n] = d.surface;
+        if (filter_index) filter_index[n] = d.filter;
+        if (unvisible_index) unvisible_index[n] = d.unvisible;
+        if (head_filter) head_filter[n] = d.head;
     }
 }
 
@@ -236,32 +223,19 @@ extern "C" int mh_launch_filter_points(MhViews vw, const float *pts, int N, int 
         for (int g = 0; g < ngroups; ++g)                                   // (per_batch <= 31, count <= 31 * batches)
             if ((long long)groups[g].count * 1 > (1 << 24)) return -1;
     }
-#define MH_F_CASE(PS)                                                                                                   \
-    case PS:                                                                                                            \
-        if (!split) {                                                                                                   \
-            hipLaunchKernelGGL(mh_filter_kernel<PS>, dim3((N + 3) / 4), dim3(256), lds, st, vw, pts, N, thr, vis_thr,      \
-                               surface_index, filter_index, unvisible_index, head_filter, bt, MhTailRows{0, 0, 0, 0});  \
-        } else {                                                                                                        \
-            hipLaunchKernelGGL(mh_filter_rows_kernel<PS>, dim3((N + 255) / 256), dim3(256), 0, st, vw, pts, N, thr,      \
-                               vis_thr, surface_index, filter_index, unvisible_index, head_filter, bt, order);         \
-            for (int g = 0; g < ngroups; ++g)                                                                           \
-                hipLaunchKernelGGL(mh_filter_kernel<PS>, dim3((groups[g].count + 3) / 4), dim3(256), lds, st, vw, pts, N, \
-                                   thr, vis_thr, surface_index, filter_index, unvisible_index, head_filter, bt,         \
-                                   groups[g]);                                                                          \
-        }                                                                                                               \
-        break;
-    switch (patch) {
-        MH_F_CASE(1)
-        MH_F_CASE(3)
-        MH_F_CASE(5)
-        MH_F_CASE(7)
-        MH_F_CASE(9)
-        MH_F_CASE(11)
-        default:
-            return -1;
-    }
-#undef MH_F_CASE
-    return (int)hipGetLastError();
+    return mh_dispatch_patch(patch, [&](auto ps) {
+        constexpr int PS = decltype(ps)::value;
+        if (!split) {
+            hipLaunchKernelGGL(mh_filter_kernel<PS>, dim3((N + 3) / 4), dim3(256), lds, st, vw, pts, N, thr, vis_thr,
+                               surface_index, filter_index, unvisible_index, head_filter, bt, MhTailRows{0, 0, 0, 0});
+        } else {
+            hipLaunchKernelGGL(mh_filter_rows_kernel<PS>, dim3((N + 255) / 256), dim3(256), 0, st, vw, pts, N, thr, vis_thr,
+                               surface_index, filter_index, unvisible_index, head_filter, bt, order);
+            for (int g = 0; g < ngroups; ++g)
+                hipLaunchKernelGGL(mh_filter_kernel<PS>, dim3((groups[g].count + 3) / 4), dim3(256), lds, st, vw, pts, N, thr,
+                                   vis_thr, surface_index, filter_index, unvisible_index, head_filter, bt, groups[g]);
+        }
+    });
 }
 
 // forces this translation unit's code object onto the device (HIP loads a fat binary on the first use of one of its kernels:

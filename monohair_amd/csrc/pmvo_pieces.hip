@@ -3,8 +3,8 @@
 // the reference's method surface -- project_points (PMVO.py:378-397), get_depth/get_ori/get_conf/get_mask/
 // get_ori_patch/get_c_patch (:482-523), compute_visible (:525-529), sample_next_3d_pos (:263-335),
 // compute_reproject_ori / compute_points_prj_ori (:219-260), compute_prj_loss (:151-209) -- with the same tensors
-// in and out.  Same arithmetic helpers as the fused kernels (mh_device.h), so the same bits.
-#include "mh_device.h"
+// in and out.  Same arithmetic helpers and front-end rules as the fused kernels (mh_device.h, mh_front.h), so the same bits.
+#include "mh_front.h"
 
 // project_points for ONE camera record: rounded+clamped (row, col), z' = -z/2, out-of-image flag, unrounded pixel
 __global__ __launch_bounds__(256) void mh_project_points_kernel(const float *__restrict__ cam,
@@ -15,20 +15,16 @@ __global__ __launch_bounds__(256) void mh_project_points_kernel(const float *__r
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const bool single = batch_rule && N == 1;   // (a batch of one point: mh_cam_project_b)
-    float u, w, z, rowf, colf;
-    mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, single);
-    mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-    int r, c;
-    const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
+    const MhCentre s = mh_centre_sample(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], H, W, single);
     if (rc) {
-        rc[2 * n] = r;
-        rc[2 * n + 1] = c;
+        rc[2 * n] = s.r;
+        rc[2 * n + 1] = s.c;
     }
-    if (zp) zp[n] = -z / 2.0f;
-    if (oobo) oobo[n] = oob ? 1 : 0;
+    if (zp) zp[n] = -s.z / 2.0f;
+    if (oobo) oobo[n] = s.oob ? 1 : 0;
     if (pixf) {
-        pixf[2 * n] = rowf;
-        pixf[2 * n + 1] = colf;
+        pixf[2 * n] = s.rowf;
+        pixf[2 * n + 1] = s.colf;
     }
 }
 
@@ -36,14 +32,14 @@ __global__ __launch_bounds__(256) void mh_project_points_kernel(const float *__r
 __global__ __launch_bounds__(256) void mh_gather_kernel(MhViews vw, int v, const long long *__restrict__ uv, int N,
                                                         int size, float4 *__restrict__ rec_out,
                                                         float *__restrict__ mask_out) {
-    const int P = size * size, hp = size / 2;
+    const int P = size * size;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)N * P) return;
     const int n = (int)(i / P), p = (int)(i - (long long)n * P);
-    const int di = p / size - hp, dj = p - (p / size) * size - hp;
+    int di, dj;
+    mh_tap_offset(p, size, di, dj);
     const int H = vw.H, W = vw.W;
-    const int r = min(max((int)uv[2 * n] + di, 0), H - 1), c = min(max((int)uv[2 * n + 1] + dj, 0), W - 1);
-    const size_t pix = (size_t)v * H * W + (size_t)r * W + c;
+    const size_t pix = (size_t)v * H * W + mh_tap_pixel((int)uv[2 * n], (int)uv[2 * n + 1], di, dj, H, W);
     if (rec_out) rec_out[i] = vw.rec[pix];
     if (mask_out) mask_out[i] = vw.mask[pix];
 }

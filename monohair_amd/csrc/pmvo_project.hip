@@ -4,7 +4,8 @@
 // HBM layout: every view is one array of 16-byte pixel records
 // {ori_row, ori_col, conf, depth} plus one fp32 mask plane.  A patch tap is ONE aligned dwordx4
 // load; the 7 (9) taps of a patch row are 112 (144) contiguous bytes.
-#include "mh_device.h"
+// The per-(view, point) rules -- centre sample, patch window, eligibility, duplicate rule, list header -- are mh_front.h's.
+#include "mh_front.h"
 
 // ---------------------------------------------------------------------------------------------
 // pack one view: reference layout (depth[H,W,Cd], ori[H,W,2], conf[H,W], mask[H,W,Cm]) -> records
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void mh_code_tabs_kernel(const float4 *__restr
 
 // ---------------------------------------------------------------------------------------------
 // PMVO.Compute_Visible_and_Ori (PMVO.py:346-376): one workgroup = one view x 64 consecutive points.
-//   phase 1: 64 lanes project their point (PMVO.project_points :378-397), fetch the centre record,
+//   phase 1: 64 lanes take the centre sample of their point (mh_centre_sample), fetch the centre record,
 //            write vis / ori / conf / mask / pixf coalesced over n;
 //   phase 2: all 256 lanes sweep the 64*P (point, tap) pairs of the tile in output order, so the
 //            ori_patch / conf_patch stores are fully coalesced (8 B + 4 B per lane) and the taps of
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void mh_project_gather_kernel(MhViews vw, cons
                                                                 float *__restrict__ ori_patch,
                                                                 float *__restrict__ conf_patch,
                                                                 float *__restrict__ pixf) {
-    constexpr int P = PATCH * PATCH, HP = PATCH / 2;
+    constexpr int P = PATCH * PATCH;
     __shared__ int s_r[MH_PG_TILE], s_c[MH_PG_TILE];
     // the grid is padded to a multiple of 8 workgroups; XCD x (= blockIdx % 8) takes the x-th eighth of the
     // (view, tile) list, i.e. a contiguous range of views
@@ -116,27 +117,18 @@ __global__ __launch_bounds__(256) void mh_project_gather_kernel(MhViews vw, cons
     if (tid < MH_PG_TILE) {
         const int n = n0 + tid;
         if (n < N) {
-            const float *cam = vw.cams + v * MH_CAM_STRIDE;
-            float u, w, z, rowf, colf;
-            mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
-            mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-            // torch.round (half to even) -> long; bounds tests on the integers (PMVO.py:383-390)
-            int r, c;
-            const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
-            s_r[tid] = r;
-            s_c[tid] = c;
-            const size_t pix = (size_t)r * W + c;
+            const MhCentre s = mh_centre_sample(vw.cams + v * MH_CAM_STRIDE, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], H, W,
+                                                vw.batch_rule && N == 1);
+            s_r[tid] = s.r;
+            s_c[tid] = s.c;
+            const size_t pix = (size_t)s.r * W + s.c;
             const float4 q = rec[pix];
             const size_t vn = (size_t)v * N + n;
-            if (vis) {
-                const float zp = -z / 2.0f;
-                float vb = mh_soft_visible(q.w, zp * 255.0f);
-                vis[vn] = oob ? -1.0f : vb;
-            }
+            if (vis) vis[vn] = mh_centre_visible(s, q);
             if (ori) reinterpret_cast<float2 *>(ori)[vn] = make_float2(q.x, q.y);
             if (conf) conf[vn] = mh_clampf(q.z, 1e-6f, 1.0f);
             if (mask) mask[vn] = vw.mask[(size_t)v * H * W + pix];
-            if (pixf) reinterpret_cast<float2 *>(pixf)[vn] = make_float2(rowf, colf);
+            if (pixf) reinterpret_cast<float2 *>(pixf)[vn] = make_float2(s.rowf, s.colf);
         }
     }
     if (!ori_patch && !conf_patch) return;
@@ -154,10 +146,9 @@ __global__ __launch_bounds__(256) void mh_project_gather_kernel(MhViews vw, cons
             const int idx = base + k * 256 + tid;
             if (idx < cnt) {
                 const int nl = idx / P, p = idx - nl * P;
-                const int i = p / PATCH - HP, j = p - (p / PATCH) * PATCH - HP;
-                const int r = min(max(s_r[nl] + i, 0), H - 1);
-                const int c = min(max(s_c[nl] + j, 0), W - 1);
-                q[k] = rec[(size_t)r * W + c];
+                int di, dj;
+                mh_tap_offset(p, PATCH, di, dj);
+                q[k] = rec[mh_tap_pixel(s_r[nl], s_c[nl], di, dj, H, W)];
             }
         }
 #pragma unroll
@@ -264,13 +255,9 @@ __global__ __launch_bounds__(64 * W) void mh_topk_wave_kernel(const float *__res
 
 // ---------------------------------------------------------------------------------------------
 // Tap lists for the search kernel.  For every (view, point) the per-tap work that does not depend on
-// the candidate sample is done ONCE here instead of 900 times in the search:
-//   - normalise the tap orientation the way torch.cosine_similarity does (PMVO.py:171),
-//   - decide which taps can ever replace the running minimum (PMVO.py:162,177-182): tap 0 always;
-//     tap p>=1 iff (patch max conf <= thr) or conf_p > thr,
-//   - compact the eligible taps in their original order (strict '<' keeps first-index tie-breaking).
-// Record (v,n): float4 header {count(bits), vis, pix_row, pix_col} followed by `count` float4 taps
-// {ox_hat, oy_hat, conf, 0}; stride (P+1) float4.  One wave per (v,n), lane = tap.
+// the candidate sample is done ONCE here instead of 900 times in the search: the tap orientations are normalised
+// (mh_unit2), the taps that can never replace the running minimum are dropped and the rest compacted in their order
+// (mh_wave_tap_list; the record layout is mh_list_header's).  One wave per (v,n), lane = tap.
 // ---------------------------------------------------------------------------------------------
 #define MH_PREP_PMAX 128
 __global__ __launch_bounds__(256) void mh_prep_taps_kernel(const float *__restrict__ ori_patch,
@@ -286,11 +273,8 @@ __global__ __launch_bounds__(256) void mh_prep_taps_kernel(const float *__restri
     if (vn >= VN) return;
     const float visv = vis[vn];
     float4 *__restrict__ out = taps + (size_t)vn * (P + 1);
-    if (visv == -1.0f) {   // the search skips this view for this point: header only
-        if (lane == 0) {
-            out[0] = make_float4(__int_as_float(0), visv, 0.0f, 0.0f);
-            cnt[vn] = 0;
-        }
+    if (visv == -1.0f) {
+        if (lane == 0) mh_list_empty(out, cnt, vn, visv);
         return;
     }
     const float *__restrict__ cp = conf_patch + (size_t)vn * P;
@@ -301,54 +285,10 @@ __global__ __launch_bounds__(256) void mh_prep_taps_kernel(const float *__restri
     for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o));
     const bool hc = cmax > thr;
     for (int b = lane; b < 256; b += MH_WAVE) s_first[wave][b] = 0xffffffffu;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // pass 1: normalise, eligibility; every eligible tap bids for "first tap with this orientation" in a
-    // 256-bucket table keyed by a hash of the unit vector's bits (one wave owns its LDS slice)
-    for (int p = lane; p < P; p += MH_WAVE) {
-        float o0, o1;
-        const float2 o = op[p];
-        mh_unit2(o.x, o.y, o0, o1);
-        const bool el = (p == 0) || (hc ? (cp[p] > thr) : true);
-        s_o[wave][p] = make_float2(o0, o1);
-        s_el[wave][p] = el;
-        if (el) {
-            const unsigned h = ((__float_as_uint(o0) * 0x9E3779B1u) ^ (__float_as_uint(o1) * 0x85EBCA77u)) >> 24;
-            atomicMin(&s_first[wave][h], (unsigned)p);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // pass 2: a tap whose unit orientation is bit-identical to an EARLIER eligible tap can never win the strict
-    // '<' of PMVO.py:177 (its loss equals that tap's for every candidate), so it is dropped -- exact, and on
-    // 8-bit orientation maps (<= 180 distinct angles) it removes most of a patch.  A hash collision only means
-    // that a duplicate survives (harmless); nothing distinct is ever dropped because the bits are compared.
-    int base = 0;
-    for (int p0 = 0; p0 < P; p0 += MH_WAVE) {
-        const int p = p0 + lane;
-        bool el = false;
-        float2 o = make_float2(0.f, 0.f);
-        if (p < P) {
-            el = s_el[wave][p] != 0;
-            o = s_o[wave][p];
-            if (el) {
-                const unsigned ox = __float_as_uint(o.x), oy = __float_as_uint(o.y);
-                const unsigned q = s_first[wave][((ox * 0x9E3779B1u) ^ (oy * 0x85EBCA77u)) >> 24];
-                if (q < (unsigned)p) {
-                    const float2 e = s_o[wave][q];
-                    if (__float_as_uint(e.x) == ox && __float_as_uint(e.y) == oy) el = false;
-                }
-            }
-        }
-        const unsigned long long m = __ballot(el);
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (el) out[1 + pos] = make_float4(o.x, o.y, cp[p], 0.0f);
-        base += __popcll(m);
-    }
+    const int base = mh_wave_tap_list<0, true>(P, lane, op, s_o[wave], cp, s_el[wave], s_first[wave], hc, thr, out);
     if (lane == 0) {
         const float2 pf = reinterpret_cast<const float2 *>(pixf)[vn];
-        out[0] = make_float4(__int_as_float(base), visv, pf.x, pf.y);
-        cnt[vn] = (uint8_t)base;   // compact copy of the list lengths [V,N]: the search's work estimate reads it coalesced
+        mh_list_header(out, cnt, vn, base, visv, pf.x, pf.y);
     }
 }
 
@@ -357,8 +297,8 @@ __global__ __launch_bounds__(256) void mh_prep_taps_kernel(const float *__restri
 // Compute_Visible_and_Ori that the base-view ranking and the sampler need) AND the tap list of the search,
 // straight from the packed maps -- the [V,N,P,..] patch tensors are never written or re-read, and for the
 // (view, point) pairs whose depth test fails (weight 0 in the loss, ~2/3 of them on a closed surface) the
-// patch is not even gathered.  Same arithmetic, same eligibility / duplicate rules and same record layout as
-// mh_project_gather_kernel + mh_prep_taps_kernel (the unfused pair, kept as the cross-check).  Two kernels:
+// patch is not even gathered.  The rules are mh_front.h's, the ones mh_project_gather_kernel + mh_prep_taps_kernel call (the
+// unfused pair, kept as the cross-check).  Two kernels:
 // mh_project_taps_codes_kernel for maps uploaded as 8-bit file codes, mh_project_taps2_kernel for fp32 records.
 // One workgroup = one view x 64 consecutive points (the tiling and XCD mapping of mh_project_gather_kernel).
 // (The first fused form -- lane = point for the whole tile, three dependent round trips per wave -- was removed in
@@ -392,7 +332,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
                                                                     const uint16_t *__restrict__ oc_all,
                                                                     const MhCodeTabs *__restrict__ tabs,
                                                                     int32_t *__restrict__ zero, int nzero) {
-    constexpr int P = PATCH * PATCH, HP = PATCH / 2, NCH = (P + MH_WAVE - 1) / MH_WAVE, PW = 16;
+    constexpr int P = PATCH * PATCH, NCH = (P + MH_WAVE - 1) / MH_WAVE, PW = 16;
     __shared__ float2 s_unit[256];
     __shared__ float s_confc[256];
     __shared__ uint8_t s_canon[256];
@@ -411,39 +351,26 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
     const float4 *__restrict__ rec = vw.rec + (size_t)v * H * W;
     const uint16_t *__restrict__ oc = oc_all + (size_t)v * H * W;
 
-    // lane = point: projection (PMVO.project_points, PMVO.py:378-397)
+    // lane = point: the centre sample
     const int n = n0 + lane;
     const bool mine = lane < PW && n < N;
-    int r = 0, c = 0;
-    float rowf = 0.0f, colf = 0.0f, z = 0.0f;
-    bool oob = true;
-    if (mine) {
-        const float *cam = vw.cams + v * MH_CAM_STRIDE;
-        float u, w;
-        mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
-        mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
-    }
+    MhCentre s = {0.0f, 0.0f, 0.0f, 0, 0, true};
+    if (mine)
+        s = mh_centre_sample(vw.cams + v * MH_CAM_STRIDE, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], H, W,
+                             vw.batch_rule && N == 1);
+    const int r = s.r, c = s.c;
+    const float rowf = s.rowf, colf = s.colf;
     float4 q0 = make_float4(0.f, 0.f, 0.f, 0.f);
     float mk = 0.0f;
     if (mine) {
         q0 = rec[(size_t)r * W + c];
         if (mask) mk = vw.mask[(size_t)v * H * W + (size_t)r * W + c];
     }
-    // per-(view, point) outputs and the depth test (soft visibility, PMVO.py:346-376)
+    // per-(view, point) outputs and the depth test
     float visv = -1.0f;
     if (mine) {
-        visv = mh_soft_visible(q0.w, (-z / 2.0f) * 255.0f);
-        visv = oob ? -1.0f : visv;
-        const size_t vn = (size_t)v * N + n;
-        vis[vn] = visv;
-        reinterpret_cast<float2 *>(ori)[vn] = make_float2(q0.x, q0.y);
-        conf[vn] = mh_clampf(q0.z, 1e-6f, 1.0f);
-        if (mask) mask[vn] = mk;
-        if (visv == -1.0f) {
-            taps[vn * (P + 1)] = make_float4(__int_as_float(0), visv, 0.0f, 0.0f);
-            cnt[vn] = 0;
-        }
+        visv = mh_centre_visible(s, q0);
+        mh_store_centre((size_t)v * N + n, visv, q0, &mk, P, vis, ori, conf, mask, taps, cnt);
     }
     // lane = tap: the patch codes of the wave's VISIBLE points, all requested back to back (up to 16 gathers in flight per
     // wave).  (Requesting the patches of all 16 points before the depth test is known takes a dependent round trip off the
@@ -452,9 +379,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
     int di[NCH], dj[NCH];
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
-        const int p = ch * MH_WAVE + lane;
-        di[ch] = p / PATCH - HP;
-        dj[ch] = p - (p / PATCH) * PATCH - HP;
+        mh_tap_offset(ch * MH_WAVE + lane, PATCH, di[ch], dj[ch]);
     }
     const int npw = min(PW, N - n0);                          // points of this wave (uniform; <= 0: nothing to do)
     unsigned k[PW][NCH];
@@ -466,7 +391,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
         for (int ch = 0; ch < NCH; ++ch) {
             k[j][ch] = 0;
             if (j < npw && vj != -1.0f && ch * MH_WAVE + lane < P)
-                k[j][ch] = oc[(size_t)min(max(rj + di[ch], 0), H - 1) * W + min(max(cj + dj[ch], 0), W - 1)];
+                k[j][ch] = oc[mh_tap_pixel(rj, cj, di[ch], dj[ch], H, W)];
         }
     }
     s_unit[tid] = t_unit;
@@ -494,7 +419,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             const int p = ch * MH_WAVE + lane;
-            el[ch] = (p < P) && ((p == 0) || (hc ? (cc[ch] > thr) : true));
+            el[ch] = (p < P) && mh_tap_eligible(p, hc, &cc[ch], thr);
             rem[ch] = __ballot(el[ch]);
             keep[ch] = 0ull;
         }
@@ -534,8 +459,7 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
         if (lane == 0) {
             const float rfj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rowf), j));
             const float cfj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(colf), j));
-            out[0] = make_float4(__int_as_float(base), vj, rfj, cfj);
-            cnt[vn] = (uint8_t)base;
+            mh_list_header(out, cnt, vn, base, vj, rfj, cfj);
         }
         }
     }
@@ -546,8 +470,8 @@ __global__ __launch_bounds__(256) void mh_project_taps_codes_kernel(MhViews vw, 
 // mh_project_taps2_kernel -- the fused front end for fp32 records in the organisation of the code form above (round 3): one
 // wave owns 16 points of the 64-point tile (lane = point for the projection, lane = tap for the patches), no workgroup
 // barrier between projection and patches, and the 16-byte patch gathers of up to INF visible points are in flight at once
-// instead of three.  Arithmetic, eligibility, duplicate rule (hash table + bit compare) and record layout are those of
-// the unfused pair mh_project_gather_kernel + mh_prep_taps_kernel: the tap lists are identical.
+// instead of three.  It calls the rules the unfused pair mh_project_gather_kernel + mh_prep_taps_kernel calls, the duplicate
+// rule (mh_wave_tap_list) among them: the tap lists are identical.
 // ---------------------------------------------------------------------------------------------
 // PW = points per wave (lane = point for the projection): 16 gives the kernel its best time alone (72 us; more waves = more
 // of their dependent chains overlap), 64 the best ITERATION (fewer, longer waves take less slot time from the search that
@@ -560,7 +484,7 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
                                                                float *__restrict__ mask, float4 *__restrict__ taps,
                                                                uint8_t *__restrict__ cnt, int32_t *__restrict__ zero,
                                                                int nzero) {
-    constexpr int P = PATCH * PATCH, HP = PATCH / 2, NCH = (P + MH_WAVE - 1) / MH_WAVE;
+    constexpr int P = PATCH * PATCH, NCH = (P + MH_WAVE - 1) / MH_WAVE;
     constexpr int INF = NCH == 1 ? 8 : 4;            // points whose patch gathers are in flight together (32 VGPRs)
     __shared__ float2 s_o[4][MH_PREP_PMAX];
     __shared__ float s_c[4][MH_PREP_PMAX];
@@ -583,23 +507,13 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
     int r = 0, c = 0;
     float rowf = 0.0f, colf = 0.0f, visv = -1.0f;
     if (mine) {
-        const float *cam = vw.cams + v * MH_CAM_STRIDE;
-        float u, w, z;
-        mh_cam_project_b(cam, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], u, w, z, vw.batch_rule && N == 1);
-        mh_ndc_to_pixel(u, w, (float)H, (float)W, rowf, colf);
-        const bool oob = mh_round_clamp_pixel(rowf, colf, H, W, r, c);
+        const MhCentre s = mh_centre_sample(vw.cams + v * MH_CAM_STRIDE, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], H, W,
+                                            vw.batch_rule && N == 1);
+        r = s.r, c = s.c, rowf = s.rowf, colf = s.colf;
         const float4 q0 = rec[(size_t)r * W + c];
-        visv = mh_soft_visible(q0.w, (-z / 2.0f) * 255.0f);
-        visv = oob ? -1.0f : visv;
-        const size_t vn = (size_t)v * N + n;
-        vis[vn] = visv;
-        reinterpret_cast<float2 *>(ori)[vn] = make_float2(q0.x, q0.y);
-        conf[vn] = mh_clampf(q0.z, 1e-6f, 1.0f);
-        if (mask) mask[vn] = vw.mask[(size_t)v * H * W + (size_t)r * W + c];
-        if (visv == -1.0f) {
-            taps[vn * (P + 1)] = make_float4(__int_as_float(0), visv, 0.0f, 0.0f);
-            cnt[vn] = 0;
-        }
+        visv = mh_centre_visible(s, q0);
+        mh_store_centre((size_t)v * N + n, visv, q0, vw.mask + (size_t)v * H * W + (size_t)r * W + c, P, vis, ori, conf, mask,
+                        taps, cnt);
     }
     const int npw = min(PW, N - n0);
     if (npw <= 0) return;
@@ -607,9 +521,7 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
     int di[NCH], dj[NCH];
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
-        const int p = ch * MH_WAVE + lane;
-        di[ch] = p / PATCH - HP;
-        dj[ch] = p - (p / PATCH) * PATCH - HP;
+        mh_tap_offset(ch * MH_WAVE + lane, PATCH, di[ch], dj[ch]);
     }
     unsigned long long todo = vmask;
     while (todo) {
@@ -627,7 +539,7 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
                 for (int ch = 0; ch < NCH; ++ch) {
                     q[k][ch] = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (ch * MH_WAVE + lane < P)
-                        q[k][ch] = tsrc[(size_t)min(max(rj + di[ch], 0), H - 1) * W + min(max(cj + dj[ch], 0), W - 1)];
+                        q[k][ch] = tsrc[mh_tap_pixel(rj, cj, di[ch], dj[ch], H, W)];
                 }
             }
         }
@@ -657,51 +569,13 @@ __global__ __launch_bounds__(256) void mh_project_taps2_kernel(MhViews vw, const
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o));
             const bool hc = cmax > thr;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (int p = lane; p < P; p += MH_WAVE) {
-                const bool el = (p == 0) || (hc ? (s_c[wave][p] > thr) : true);
-                s_el[wave][p] = el;
-                if (el) {
-                    const float2 o = s_o[wave][p];
-                    const unsigned h = ((__float_as_uint(o.x) * 0x9E3779B1u) ^ (__float_as_uint(o.y) * 0x85EBCA77u)) >> 24;
-                    atomicMin(&s_first[wave][h], (unsigned)p);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            int base = 0;
-            for (int p0 = 0; p0 < P; p0 += MH_WAVE) {
-                const int p = p0 + lane;
-                bool el = false;
-                float2 o = make_float2(0.f, 0.f);
-                float cc = 0.f;
-                if (p < P) {
-                    el = s_el[wave][p] != 0;
-                    o = s_o[wave][p];
-                    cc = s_c[wave][p];
-                    if (el) {
-                        const unsigned ox = __float_as_uint(o.x), oy = __float_as_uint(o.y);
-                        const unsigned qf = s_first[wave][((ox * 0x9E3779B1u) ^ (oy * 0x85EBCA77u)) >> 24];
-                        if (qf < (unsigned)p) {
-                            const float2 e = s_o[wave][qf];
-                            if (__float_as_uint(e.x) == ox && __float_as_uint(e.y) == oy) el = false;
-                        }
-                    }
-                }
-                const unsigned long long m = __ballot(el);
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                if (el) out[1 + pos] = make_float4(o.x, o.y, cc, 0.0f);
-                base += __popcll(m);
-            }
+            const int base = mh_wave_tap_list<P, false>(P, lane, nullptr, s_o[wave], s_c[wave], s_el[wave], s_first[wave], hc,
+                                                        thr, out);
             const float vjj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(visv), j));
             const float rfj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rowf), j));
             const float cfj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(colf), j));
-            if (lane == 0) {
-                out[0] = make_float4(__int_as_float(base), vjj, rfj, cfj);
-                cnt[vn] = (uint8_t)base;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            if (lane == 0) mh_list_header(out, cnt, vn, base, vjj, rfj, cfj);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the next point reuses the wave's LDS slices)
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -740,23 +614,10 @@ extern "C" int mh_launch_project_gather(MhViews vw, const float *pts, int N, int
                                         float *pixf, hipStream_t st) {
     const int tiles = (N + MH_PG_TILE - 1) / MH_PG_TILE;
     const dim3 grid((vw.V * tiles + 7) & ~7), block(256);
-#define MH_PG_CASE(PS)                                                                                          \
-    case PS:                                                                                                    \
-        hipLaunchKernelGGL(mh_project_gather_kernel<PS>, grid, block, 0, st, vw, pts, N, tiles, vis, ori, conf,  \
-                           mask, ori_patch, conf_patch, pixf);                                                  \
-        break;
-    switch (patch) {
-        MH_PG_CASE(1)
-        MH_PG_CASE(3)
-        MH_PG_CASE(5)
-        MH_PG_CASE(7)
-        MH_PG_CASE(9)
-        MH_PG_CASE(11)
-        default:
-            return -1;
-    }
-#undef MH_PG_CASE
-    return (int)hipGetLastError();
+    return mh_dispatch_patch(patch, [&](auto ps) {
+        hipLaunchKernelGGL(mh_project_gather_kernel<decltype(ps)::value>, grid, block, 0, st, vw, pts, N, tiles, vis, ori,
+                           conf, mask, ori_patch, conf_patch, pixf);
+    });
 }
 
 // wk.cls != nullptr (the fused forward; wave form only): the kernel also writes the work classes of the search's launch order
@@ -817,33 +678,21 @@ extern "C" int mh_launch_project_taps(MhViews vw, const float *pts, int N, int p
     const int pw = codes ? 16 : (tile == 16 || tile == 32 ? tile : 64);
     const int tiles = (N + 4 * pw - 1) / (4 * pw);
     const dim3 grid((vw.V * tiles + 7) & ~7), block(256);
-#define MH_PT_CASE(PS)                                                                                             \
-    case PS:                                                                                                       \
-        if (codes)                                                                                                 \
-            hipLaunchKernelGGL((mh_project_taps_codes_kernel<PS>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, \
-                               conf, mask, taps, cnt, oc, tabs, zero, nzero);                                      \
-        else if (pw == 64)                                                                                         \
-            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 64>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf, \
-                               mask, taps, cnt, zero, nzero);                                                     \
-        else if (pw == 32)                                                                                         \
-            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 32>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf, \
-                               mask, taps, cnt, zero, nzero);                                                     \
-        else                                                                                                       \
-            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 16>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf, \
-                               mask, taps, cnt, zero, nzero);                                                     \
-        break;
-    switch (patch) {
-        MH_PT_CASE(1)
-        MH_PT_CASE(3)
-        MH_PT_CASE(5)
-        MH_PT_CASE(7)
-        MH_PT_CASE(9)
-        MH_PT_CASE(11)
-        default:
-            return -1;
-    }
-#undef MH_PT_CASE
-    return (int)hipGetLastError();
+    return mh_dispatch_patch(patch, [&](auto ps) {
+        constexpr int PS = decltype(ps)::value;
+        if (codes)
+            hipLaunchKernelGGL((mh_project_taps_codes_kernel<PS>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf,
+                               mask, taps, cnt, oc, tabs, zero, nzero);
+        else if (pw == 64)
+            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 64>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf,
+                               mask, taps, cnt, zero, nzero);
+        else if (pw == 32)
+            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 32>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf,
+                               mask, taps, cnt, zero, nzero);
+        else
+            hipLaunchKernelGGL((mh_project_taps2_kernel<PS, 16>), grid, block, 0, st, vw, pts, N, tiles, thr, vis, ori, conf,
+                               mask, taps, cnt, zero, nzero);
+    });
 }
 
 // forces this translation unit's code object onto the device (HIP loads a fat binary on the first use of one of its kernels:

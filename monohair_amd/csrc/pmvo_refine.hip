@@ -1,8 +1,9 @@
 // pmvo_refine.hip -- the losses of PMVO.refine (PMVO.py:86-92) and of refine's smoothing loop (PMVO.py:602-650), gfx950 only:
 // the loss of ONE given direction per point from gathered patches (mh_refine_loss_kernel) or straight from the maps
 // (mh_refine_loss_maps_kernel), and the combine step of the smoothing loop (mh_refine_combine_kernel).  They share nothing
-// with the search (pmvo_search.hip) but mh_device.h.
-#include "mh_device.h"
+// with the search (pmvo_search.hip) but mh_device.h; the maps kernel takes its centre sample, patch window and tap eligibility
+// from mh_front.h.
+#include "mh_front.h"
 
 // ---------------------------------------------------------------------------------------------
 // PMVO.refine's loss of ONE given direction per point (PMVO.py:86-90): next = p + dir*mul/div,
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
                                                                   const float *__restrict__ dir, float mul, float dv,
                                                                   int N, float thr, float *__restrict__ loss,
                                                                   uint8_t *__restrict__ hcout, MhBatch bt) {
-    constexpr int P = PATCH * PATCH, HP = PATCH / 2, ROUNDS = (P + MH_WAVE - 1) / MH_WAVE;
+    constexpr int P = PATCH * PATCH, ROUNDS = (P + MH_WAVE - 1) / MH_WAVE;
     __shared__ float s_num[4][MH_REFINE_VMAX], s_den[4][MH_REFINE_VMAX];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + wave;
@@ -125,11 +126,7 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
     const bool single = bt.single_ok && one_point;
     int ti[ROUNDS], tj[ROUNDS];
 #pragma unroll
-    for (int t = 0; t < ROUNDS; ++t) {
-        const int p = min(lane + MH_WAVE * t, P - 1);
-        ti[t] = p / PATCH - HP;
-        tj[t] = p - (p / PATCH) * PATCH - HP;
-    }
+    for (int t = 0; t < ROUNDS; ++t) mh_tap_offset(min(lane + MH_WAVE * t, P - 1), PATCH, ti[t], tj[t]);
     auto rdf = [](float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); };
     for (int v0 = 0; v0 < V; v0 += MH_WAVE) {
         const int v = v0 + lane;
@@ -137,12 +134,11 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
         int r = 0, c = 0;
         if (v < V) {
             const float *cam = vw.cams + v * MH_CAM_STRIDE;
-            float u, w, z, r0, c0;
-            mh_cam_project_b(cam, P0, P1, P2, u, w, z, single);
-            mh_ndc_to_pixel(u, w, Hf, Wf, r0, c0);
-            const bool oob = mh_round_clamp_pixel(r0, c0, H, W, r, c);
+            const MhCentre s = mh_centre_sample(cam, P0, P1, P2, H, W, single);
+            const float r0 = s.rowf, c0 = s.colf;
+            r = s.r, c = s.c;
             const float4 q = vw.rec[(size_t)v * H * W + (size_t)r * W + c];
-            visv = oob ? -1.0f : mh_soft_visible(q.w, (-z / 2.0f) * 255.0f);
+            visv = mh_centre_visible(s, q);
             if (visv != -1.0f) {
                 float r1, c1;
                 mh_pixel_of_b(cam, Q0, Q1, Q2, Hf, Wf, r1, c1, single);
@@ -164,14 +160,14 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
             const size_t base = (size_t)(v0 + src) * H * W;
 #pragma unroll
             for (int t = 0; t < ROUNDS; ++t) {
-                const int r2 = min(max(rv + ti[t], 0), H - 1), c2 = min(max(cv + tj[t], 0), W - 1);
+                const size_t pix = base + mh_tap_pixel(rv, cv, ti[t], tj[t], H, W);
                 if (vw.tap) {   // (the plane of ready-made taps, MhViews::tap: the same values, made once at upload)
-                    const float4 tq = vw.tap[base + (size_t)r2 * W + c2];
+                    const float4 tq = vw.tap[pix];
                     a0[t] = tq.x;
                     a1[t] = tq.y;
                     ac[t] = tq.z;
                 } else {
-                    const float4 tq = vw.rec[base + (size_t)r2 * W + c2];
+                    const float4 tq = vw.rec[pix];
                     mh_unit2(tq.x, tq.y, a0[t], a1[t]);
                     ac[t] = mh_clampf(tq.z, 1e-6f, 1.0f);
                 }
@@ -213,7 +209,7 @@ __global__ __launch_bounds__(256) void mh_refine_loss_maps_kernel(MhViews vw, co
                 const float cs = o0[t] * dxv + o1[t] * dyv;
                 const float l = 1.0f - __builtin_fabsf(cs);
                 if (t == 0) l0 = l;
-                const bool cand = p < P && (p == 0 || ((hc ? (cf[t] > thr) : true) && l == l));
+                const bool cand = p < P && mh_tap_eligible(p, hc, &cf[t], thr) && (p == 0 || l == l);
                 if (cand && (bp == 0x7fffffff || l < bl)) {   // (rounds ascend in p: a tie keeps the earlier tap)
                     bl = l;
                     bp = p;
@@ -310,22 +306,10 @@ extern "C" int mh_launch_refine_loss_maps(MhViews vw, const float *pts, const fl
     if (vw.V > MH_REFINE_VMAX) return -1;
     const MhBatch bt = {row0, total, batch, sum_block, vw.batch_rule};
     const dim3 grid((N + 3) / 4), block(256);
-#define MH_RM_CASE(PS)                                                                                               \
-    case PS:                                                                                                         \
-        hipLaunchKernelGGL(mh_refine_loss_maps_kernel<PS>, grid, block, 0, st, vw, pts, dir, mul, dv, N, thr, loss, hc, bt); \
-        break;
-    switch (patch) {
-        MH_RM_CASE(1)
-        MH_RM_CASE(3)
-        MH_RM_CASE(5)
-        MH_RM_CASE(7)
-        MH_RM_CASE(9)
-        MH_RM_CASE(11)
-        default:
-            return -1;
-    }
-#undef MH_RM_CASE
-    return (int)hipGetLastError();
+    return mh_dispatch_patch(patch, [&](auto ps) {
+        hipLaunchKernelGGL(mh_refine_loss_maps_kernel<decltype(ps)::value>, grid, block, 0, st, vw, pts, dir, mul, dv, N, thr,
+                           loss, hc, bt);
+    });
 }
 
 extern "C" int mh_launch_refine_combine(const float *center, const float *loss_u, const uint8_t *head,
