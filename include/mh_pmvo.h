@@ -676,6 +676,70 @@ int mh_volume_match(mh_ctx *ctx, const long long *q_voxels, const float *q_ori, 
                     const float *t_ori, const int32_t *dims, const int32_t *reach, const double *cos2, int n_pairs,
                     uint8_t *out_flags, void *stream);
 
+/* Inner fill (monohair_amd.hairfill; no counterpart in the reference, whose interior is the output of a network): the voxels
+ * that lie inside the hair, outside the head and are seen by almost no view, and the exterior volume's orientations carried
+ * inward to them -- the rows of `ours/raw.npy` the second pass merges (PMVO.py:733-751).  voxel_min [3] and voxel_size are HOST
+ * float64 (finite, voxel_size > 0), dims = (X, Y, Z) HOST int32 with X*Y*Z < 2^31.  The votes compare float32 values as the vote
+ * kernels do; everything else is float64 arithmetic on float32 inputs, + - * / sqrt in the order written, nothing fused.  The
+ * rule has three parts.
+ *
+ * 1. Domain votes, for the centre of every voxel (x, y, z) of the grid.  Its world point is the inverse of p2v: w = (vmin.x +
+ *   x*vs, -(vmin.y + y*vs), -(vmin.z + z*vs)) in float64, each component rounded once to float32.  For every view of the context
+ *   (fp32 planes or 8-bit codes) w is projected and its pixel p rounded and clamped by the rule of the vote kernels
+ *   (PMVO.project_points, PMVO.py:378-397: Camera.projection, ndc -> pixel, round half to even, the bounds tests on the
+ *   integers); z' = -z_camera / 2 and z255 = z' * 255 in float32 as the votes form them.  A view ABSTAINS if the pixel is out of
+ *   the image (out_index) or the point is not in front of the camera (not z' > 0; a NaN point abstains everywhere).  Otherwise
+ *     visible = not (z255 - depth[p] > 0.9)        the float32 comparison of compute_unvisible_points, PMVO.py:470
+ *     front   = z255 <= bust[p]                    bust: float32 [V,H,W], the depth plane of the bust ALONE in PMVO's depth
+ *                                                  convention, 255 where there is none; equality counts as in front
+ *     hair    = mask[p] > 0.2                      as the votes read the mask
+ *   and the voxel's four int32 counts are n_in (views that do not abstain), n_vis (visible), n_front (front) and n_bad (front
+ *   and not hair).  The voxel is in the DOMAIN iff n_in >= 1, n_vis <= 2 (the reference's "seen by at most two views"), n_front
+ *   >= 1 (a voxel behind the bust's front surface in every view is inside the head), n_bad <= max_bad (0: no free line of sight
+ *   ends on a pixel that is not hair) and it is not a voxel of the exterior volume.  This is a visual-hull test, not an inside
+ *   test of the bust: it wrongly excludes hair in a concavity of the hull such as the one between neck and shoulder, where some
+ *   view sees past the hair onto a pixel that is not hair.  The domain list is the flagged voxels ascending by (x*Y + y)*Z + z
+ *   (mh_select_rows on the flags).
+ * 2. Orientation sweeps.  An exterior voxel with float32 direction a has the tensor of the six products qx*qx, qy*qy, qz*qz,
+ *   qx*qy, qx*qz, qy*qz of q = rint(4096 * a) per component, half to even, as integers (exact in float64).  A voxel whose
+ *   direction is not finite, whose q is 0, or with a |q| component above 2^26 (the products would not be exact) is no SOURCE: it
+ *   counts as absent.  A dense int32 map over the grid holds for every cell a domain row, an exterior row or nothing; the two
+ *   lists must be unique, inside the grid and disjoint (status counts the offenders: the caller raises).  Per domain row there
+ *   are six float64 T and a byte `known`, all zero at the start, each twice (ping-pong).  Sweep k = 1 .. sweeps updates every
+ *   domain row from the buffers of sweep k-1: over the neighbours in the fixed order (x-1), (x+1), (y-1), (y+1), (z-1), (z+1),
+ *   those outside the grid not existing, S = the sum in that order (from 0) of the tensors of the neighbours that are exterior
+ *   sources or known domain rows, c = their number.  If c > 0: T = S / c per component, known = 1, and depth = k if the row was
+ *   unknown; otherwise the row is carried over unchanged.  One lane per row, no atomics: a permuted domain list gives the
+ *   permuted result.
+ * 3. Resolve.  Each known row is resolved by the Resolve rule of "Strand volume" on M = T (the same device function,
+ *   csrc/mh_volume.h): trace, the first-largest-diagonal column, 24 power steps, coh = v.(M v) / trace, v.y > 0 -> -v, ori =
+ *   float32(v); rows that are unknown or have trace = 0 get ori = 0 and coh = 0.  A row is EMITTED iff it is known, trace > 0
+ *   and coh >= min_coh (HOST float64, not NaN).  An output row is [w (float32), ori, 1.0], the seven columns of raw.npy, in
+ *   domain order.
+ *
+ * mh_inner_votes: bust [V,H,W] float32 on the device, the views of ctx -> counts [X*Y*Z][4] int32 = {n_in, n_vis, n_front,
+ *   n_bad} per voxel (x*Y + y)*Z + z.
+ * mh_inner_domain: counts and ext_index [X*Y*Z] (mh_volume_index of the exterior voxels, or NULL: no exterior) -> flags
+ *   [X*Y*Z] uint8.
+ * mh_inner_diffuse: ext_voxels [n_ext,3] / dom_voxels [n_dom,3] int64, ext_ori [n_ext,3] float32, 0 <= sweeps <= 1024 -> map
+ *   [X*Y*Z] int32 (domain row d: d + 1, exterior row e: -(e + 1), 0: none), ext_tensor [n_ext,6] float64, ext_source [n_ext]
+ *   uint8, cell [n_dom] int32 (the row's (x*Y + y)*Z + z, -1 outside the grid), tensor [n_dom,6] float64 and known [n_dom] uint8
+ *   = the state after the last sweep (tensor_b / known_b: the other half of the ping-pong, same sizes), depth [n_dom] int32 (0:
+ *   never reached), status (device int32 [2]) = {voxels outside the grid, voxels whose cell was already taken}.
+ * mh_inner_resolve: -> world [n_dom,3] and ori [n_dom,3] float32, coh [n_dom] float64, emit [n_dom] uint8; the emitted rows
+ *   are compacted by mh_select_rows(emit, a = world, b = ori). */
+int mh_inner_votes(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                   int32_t *counts, void *stream);
+int mh_inner_domain(mh_ctx *ctx, const int32_t *counts, const int32_t *ext_index, const int32_t *dims, int max_bad,
+                    uint8_t *flags, void *stream);
+int mh_inner_diffuse(mh_ctx *ctx, const long long *ext_voxels, const float *ext_ori, int n_ext, const long long *dom_voxels,
+                     int n_dom, const int32_t *dims, int sweeps, int32_t *map, double *ext_tensor, uint8_t *ext_source,
+                     int32_t *cell, double *tensor, double *tensor_b, uint8_t *known, uint8_t *known_b, int32_t *depth,
+                     int32_t *status, void *stream);
+int mh_inner_resolve(mh_ctx *ctx, const long long *dom_voxels, int n_dom, const double *tensor, const uint8_t *known,
+                     const double *voxel_min, double voxel_size, const int32_t *dims, double min_coh, float *world, float *ori,
+                     double *coh, uint8_t *emit, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

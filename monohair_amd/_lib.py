@@ -94,7 +94,11 @@ _SIGS = {
     "mh_strand_volume_resolve": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mh_volume_index": (ci, [vp, vp, ci, vp, vp, vp, vp]),
     "mh_volume_match": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp]),
-    "mh_knn_grid": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "mh_inner_votes": (ci, [vp, vp, vp, ctypes.c_double, vp, vp, vp]),
+    "mh_inner_domain": (ci, [vp, vp, vp, vp, ci, vp, vp]),
+    "mh_inner_diffuse": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mh_inner_resolve": (ci, [vp, vp, ci, vp, vp, vp, ctypes.c_double, vp, ctypes.c_double, vp, vp, vp, vp, vp]),
+    "mh_knn_grid":(ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),
     "mh_grid_scratch_bytes": (csz, [ci]),

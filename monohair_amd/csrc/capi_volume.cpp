@@ -1,4 +1,5 @@
-// capi_volume.cpp -- C ABI of the strand volume and the volume scores (csrc/hairvolume.hip; no counterpart in the reference)
+// capi_volume.cpp -- C ABI of the strand volume, the volume scores (csrc/hairvolume.hip) and the inner fill (csrc/hairfill.hip);
+// none has a counterpart in the reference
 #include <cmath>
 
 #include "mh_capi.h"
@@ -69,4 +70,63 @@ extern "C" int mh_volume_match(mh_ctx *ctx, const long long *q_voxels, const flo
     return launched(mh_launch_volume_match(q_voxels, q_ori, nq, t_index, t_ori, dims[0], dims[1], dims[2], pr, out_flags,
                                            (hipStream_t)stream),
                     "mh_volume_match");
+}
+
+// ---- the inner fill (csrc/hairfill.hip; include/mh_pmvo.h, "Inner fill")
+static bool vol_grid(MhVolGrid *gr, const double *voxel_min, double voxel_size, const int32_t *dims) {
+    if (!voxel_min || !vol_dims_ok(dims) || !(voxel_size > 0.0 && std::isfinite(voxel_size))) return false;
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(voxel_min[c])) return false;
+        gr->bust[c] = 0.0, gr->vmin[c] = voxel_min[c];
+    }
+    gr->vs = voxel_size;
+    gr->X = dims[0], gr->Y = dims[1], gr->Z = dims[2];
+    return true;
+}
+
+extern "C" int mh_inner_votes(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                              int32_t *counts, void *stream) {
+    if (!ctx || !ctx->rec || !ctx->mask || !ctx->cams || ctx->V < 1) return fail(MH_ERR_STATE, "mh_inner_votes: views not set");
+    MhVolGrid gr;
+    if (!bust || !counts || !vol_grid(&gr, voxel_min, voxel_size, dims)) return fail(MH_ERR_ARG, "mh_inner_votes: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_inner_votes(ctx->views(), bust, gr, counts, (hipStream_t)stream), "mh_inner_votes");
+}
+
+extern "C" int mh_inner_domain(mh_ctx *ctx, const int32_t *counts, const int32_t *ext_index, const int32_t *dims, int max_bad,
+                               uint8_t *flags, void *stream) {
+    if (!ctx || !counts || !vol_dims_ok(dims) || !flags || max_bad < 0) return fail(MH_ERR_ARG, "mh_inner_domain: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_inner_domain(counts, ext_index, (size_t)dims[0] * dims[1] * dims[2], max_bad, flags,
+                                           (hipStream_t)stream),
+                    "mh_inner_domain");
+}
+
+extern "C" int mh_inner_diffuse(mh_ctx *ctx, const long long *ext_voxels, const float *ext_ori, int n_ext,
+                                const long long *dom_voxels, int n_dom, const int32_t *dims, int sweeps, int32_t *map,
+                                double *ext_tensor, uint8_t *ext_source, int32_t *cell, double *tensor, double *tensor_b,
+                                uint8_t *known, uint8_t *known_b, int32_t *depth, int32_t *status, void *stream) {
+    if (!ctx || !vol_dims_ok(dims) || !map || !status || n_ext < 0 || n_dom < 0 || sweeps < 0 || sweeps > MH_FILL_MAXSWEEPS ||
+        (n_ext > 0 && (!ext_voxels || !ext_ori || !ext_tensor || !ext_source)) ||
+        (n_dom > 0 && (!dom_voxels || !cell || !tensor || !tensor_b || !known || !known_b || !depth)))
+        return fail(MH_ERR_ARG, "mh_inner_diffuse: bad arguments (0 <= sweeps <= %d)", MH_FILL_MAXSWEEPS);
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_inner_diffuse(ext_voxels, ext_ori, n_ext, dom_voxels, n_dom, dims[0], dims[1], dims[2], sweeps, map,
+                                            ext_tensor, ext_source, cell, tensor, tensor_b, known, known_b, depth, status,
+                                            (hipStream_t)stream),
+                    "mh_inner_diffuse");
+}
+
+extern "C" int mh_inner_resolve(mh_ctx *ctx, const long long *dom_voxels, int n_dom, const double *tensor, const uint8_t *known,
+                                const double *voxel_min, double voxel_size, const int32_t *dims, double min_coh, float *world,
+                                float *ori, double *coh, uint8_t *emit, void *stream) {
+    if (n_dom == 0) return MH_OK;
+    MhVolGrid gr;
+    if (!ctx || n_dom < 0 || !dom_voxels || !tensor || !known || !vol_grid(&gr, voxel_min, voxel_size, dims) ||
+        std::isnan(min_coh) || !world || !ori || !coh || !emit)
+        return fail(MH_ERR_ARG, "mh_inner_resolve: bad arguments");
+    MH_HIP(hipSetDevice(ctx->device));
+    return launched(mh_launch_inner_resolve(dom_voxels, n_dom, tensor, known, gr, min_coh, world, ori, coh, emit,
+                                            (hipStream_t)stream),
+                    "mh_inner_resolve");
 }

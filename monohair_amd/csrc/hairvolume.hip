@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "mh_device.h"
+#include "mh_volume.h"
 
 // the strand of point i: the s with offs[s] <= i < offs[s+1] (offs non-decreasing, offs[0] = 0); S when i is beyond them
 __device__ __forceinline__ int mh_vol_strand_of(const int64_t *__restrict__ offs, int S, int64_t i) {
@@ -124,17 +125,7 @@ __global__ __launch_bounds__(256) void mh_strand_volume_resolve_kernel(const lon
         return;
     }
     double x, y, z;
-    if (xx >= yy && xx >= zz) x = xx, y = xy, z = xz;
-    else if (yy >= zz) x = xy, y = yy, z = yz;
-    else x = xz, y = yz, z = zz;
-    for (int it = 0; it < 24; ++it) {
-        const double mx = (xx * x + xy * y) + xz * z, my = (xy * x + yy * y) + yz * z, mz = (xz * x + yz * y) + zz * z;
-        const double len = sqrt((mx * mx + my * my) + mz * mz);
-        x = mx / len, y = my / len, z = mz / len;
-    }
-    const double mx = (xx * x + xy * y) + xz * z, my = (xy * x + yy * y) + yz * z, mz = (xz * x + yz * y) + zz * z;
-    coh[g] = ((x * mx + y * my) + z * mz) / trace;
-    if (y > 0.0) x = -x, y = -y, z = -z;
+    coh[g] = mh_tensor_axis(xx, yy, zz, xy, xz, yz, trace, x, y, z);      // (mh_volume.h: shared with hairfill.hip)
     o[0] = (float)x, o[1] = (float)y, o[2] = (float)z;
 }
 

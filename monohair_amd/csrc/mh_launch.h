@@ -70,8 +70,10 @@ struct MhVolPairs {                   // pair k: Chebyshev radius in voxels, squ
     int reach[MH_VOL_MAXK];
     int K;
 };
+#define MH_FILL_MAXQ 67108864.0       // inner fill: |q| = |rint(4096 a)| up to 2^26 has exact products in int64 and float64
+#define MH_FILL_MAXSWEEPS 1024
 
-struct MhRVert;    // raster.hip: a transformed mesh vertex (16 B)
+struct MhRVert;   // raster.hip: a transformed mesh vertex (16 B)
 struct MhRLVert;   // raster.hip: a transformed strand vertex (32 B)
 
 // What one launch of the search does, decoded once from the lab option "search_variant" (include/mh_pmvo_lab.h) by capi.cpp.
@@ -338,4 +340,14 @@ int mh_launch_volume_index(const long long *voxels, int G, int X, int Y, int Z, 
                            hipStream_t st);
 int mh_launch_volume_match(const long long *q_vox, const float *q_ori, int nq, const int32_t *t_index, const float *t_ori,
                            int X, int Y, int Z, MhVolPairs pr, uint8_t *out, hipStream_t st);
+// hairfill.hip
+int mh_launch_inner_votes(MhViews vw, const float *bust, MhVolGrid gr, int32_t *counts, hipStream_t st);
+int mh_launch_inner_domain(const int32_t *counts, const int32_t *ext_index, size_t nvox, int max_bad, uint8_t *flags,
+                           hipStream_t st);
+int mh_launch_inner_diffuse(const long long *ext_voxels, const float *ext_ori, int n_ext, const long long *dom_voxels, int n_dom,
+                            int X, int Y, int Z, int sweeps, int32_t *map, double *ext_tensor, uint8_t *ext_source,
+                            int32_t *cell, double *t_a, double *t_b, uint8_t *known_a, uint8_t *known_b, int32_t *depth,
+                            int32_t *status, hipStream_t st);
+int mh_launch_inner_resolve(const long long *dom_voxels, int n_dom, const double *tensor, const uint8_t *known, MhVolGrid gr,
+                            double min_coh, float *world, float *ori, double *coh, uint8_t *emit, hipStream_t st);
 }
