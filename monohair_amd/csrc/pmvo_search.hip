@@ -12,8 +12,9 @@
 // and first tap: scalar loads; the rest: broadcast vector loads, what the backend selects for the ping-pong
 // groups) and the inner loop is pure VALU: per (item, tap) 2 mul + add + (1-|x|) + cmp + 2 cndmask in the portable kernel and
 // the select body of the shipped one; its key body keeps the running (loss, tap) minimum as one integer key per item and
-// needs 2 mul + add + sub + lshl_or + half a min3 (see mh_tap_key); a list's last tap seeds the minimum instead of padding
-// a four-tap block (see mh_key_walked).
+// needs 2 mul + add + sub + lshl_or + half a min3 (see MH_KEY_C) -- for patches up to 8 x 8 the key is that of a four-tap
+// block, 2 mul + add + sub per tap and min, min3, lshl_or + half a min3 per block (see mh_seed_key); a list's last tap
+// seeds the minimum instead of padding a four-tap block (see mh_key_walked).
 // Views in which the point is not visible (vis == -1 => weight 0, PMVO.py:212) are skipped: adding
 // their exact zeros would not change any sum.
 #include "mh_search_common.h"
@@ -315,14 +316,23 @@ __device__ __forceinline__ void mh_tap_update(float (&ML)[KA], float (&BC)[KA], 
 // one's; its tap = 2 * place + parity.  A later group replaces an earlier one only on a strictly smaller loss.  mul, mul,
 // add, sub, lshl_or per evaluation + half a min3: 5.5 instructions instead of 7, two accumulators per item, one compare
 // and two selects per (item, view) to merge them.
+// The one-group kernels (patch <= 8 x 8: !BIGP) key the four-tap BLOCK instead of the tap (mh_key_blockm4): the tap's place is
+// wanted once per (item, view), for the winner, and lshl_or and min3 issue at half the rate of mul / add / sub.  The four t' of
+// a block as above, m = their minimum on the raw bits (positive floats: monotone), key = (m << 4) | block (16 blocks of a
+// 64-tap group; the top bit of the key, the last of the constant 0b00111, stays set), ONE accumulator per item, the key of a
+// block kept until the next block folds both with one v_min3_u32: per block and item 16 full-rate + min, min3, lshl_or + half
+// a min3 = 3.5 half-rate instructions instead of 6.  An earlier block wins a tie in m by its smaller number.  After the walk
+// the lane reads the taps of ITS winning block again (per-lane LDS addresses), makes their t' again -- the same instructions
+// on the same operands -- and takes the first that equals m: the lexicographic minimum of (loss, tap) as before.
 // What the key cannot state -- a winner with x <= 2^-14 (t' >= 1 lands on the coarser grid of [1, 2)), a NaN -- shows as
-// key >= MH_KEY_BAD; a wave that sees one on any of its lanes evaluates that view again with the compare-and-select body
+// key >= MH_KEY_BAD (MH_KEY_BAD_TAP for the per-tap keys); a wave that sees one on any of its lanes evaluates that view again with the compare-and-select body
 // (mh_tap_update), which is also what runs for one-tap lists and for a NaN seed tap.  Both bodies give the same bits
 // wherever the key is valid, so the outputs are those of the select body everywhere.
 // ---------------------------------------------------------------------------------------------
 #define MH_KEY_C 1.00006103515625f   // 1 + 2^-14
 #define MH_KEY_E 6.103515625e-05f    // 2^-14
-#define MH_KEY_BAD 0xF0000000u       // key of t' = 1.0 (index 0)
+#define MH_KEY_BAD 0xF8000000u       // block key of t' = 1.0 (block 0)
+#define MH_KEY_BAD_TAP 0xF0000000u   // per-tap key of t' = 1.0 (place 0)
 #ifndef MH_KEY_MIN_TAPS
 #define MH_KEY_MIN_TAPS 10           // lists up to this length go through the select body directly
 #endif
@@ -365,11 +375,16 @@ extern "C" int mh_debug_key_stats(unsigned long long *out, int reset) {
 #else
 #define MH_KEY_COUNT(i) do { } while (0)
 #endif
-__device__ __forceinline__ unsigned mh_tap_key(float cs, int idx) {
+__device__ __forceinline__ float mh_key_tprime(float cs) {
     float t;
-    unsigned k;
     asm("v_sub_f32_e64 %0, %2, |%1|" : "=v"(t) : "v"(cs), "s"(MH_KEY_C));
-    asm("v_lshl_or_b32 %0, %1, 5, %2" : "=v"(k) : "v"(t), "s"(idx));
+    return t;
+}
+// the block key of ONE tap (the seeded last tap of a list): its t' under the number of its block
+__device__ __forceinline__ unsigned mh_seed_key(float cs, int blk) {
+    const float t = mh_key_tprime(cs);
+    unsigned k;
+    asm("v_lshl_or_b32 %0, %1, 4, %2" : "=v"(k) : "v"(t), "s"(blk));
     return k;
 }
 __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c) {
@@ -378,7 +393,8 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
     return r;
 }
 
-// Four taps x NI items of the key body as ONE hand-ordered block: per item 16 full-rate (mul, mul, add, sub) + 4 v_lshl_or +
+// Four taps x NI items of the per-tap key body as ONE hand-ordered block (mh_key_block4; the block-key body's mh_key_blockm4 is
+// made the same way, two items at a time: with four the headline kernel spills): per item 16 full-rate (mul, mul, add, sub) + 4 v_lshl_or +
 // 2 v_min3 (88 instructions for four items), every result used at least NI - 1 instructions after it is produced.  (Left to
 // the compiler as one asm statement per instruction, its hazard recogniser pads every inline-asm result that is read by
 // the very next instruction with an s_nop -- it cannot see that no dst_sel is involved: ~9 per block.)  The "memory"
@@ -742,13 +758,91 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
         if constexpr (!KEYS) {
             select_body();
         } else {
-            // the key body (see mh_tap_key): taps in groups of 64, blocks of MH_KEY_PAD taps (see mh_key_walked)
+            // the key body (see MH_KEY_C): taps in groups of 64, blocks of MH_KEY_PAD taps (see mh_key_walked)
             // uniform: a short list (the key body's fixed cost per view -- padding, decode -- only pays from about a dozen
             // taps on: lists of 8-bit maps are mostly shorter, lists of continuous maps hardly ever) / a NaN seed tap
             bool again = (ntap <= MH_KEY_MIN_TAPS) || !(t0.x == t0.x && t0.y == t0.y);
             MH_KEY_COUNT(0);
             if (again) MH_KEY_COUNT(1);
-            if (!again) {
+            if constexpr (!BIGP) {
+              if (!again) {
+                // patch <= 8x8, one 64-tap group: the block-key body (see mh_seed_key) -- one accumulator per item, the
+                // key of a block in kk until the next block folds both with one v_min3_u32
+                const int ntp = mh_key_walked<false>(ntap);
+                unsigned acc[KN], kk[KN];
+                const unsigned rec1 = (unsigned)(size_t)(const __attribute__((address_space(3))) float4 *)(rec + 1);
+                static_assert(MH_KEY_PAD == 4 && GRP == 4, "the key block takes four taps");
+                {
+                    // (tx, ty) of tap i is the first half of record 1 + i
+                    const float2 *__restrict__ t2 = reinterpret_cast<const float2 *>(rec + 1);
+                    float2 ga[GRP], gb[GRP];
+#pragma unroll
+                    for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * u];
+                    // the list's last tap seeds the accumulator, under its own block's number
+                    const int is = ntap - 1;
+                    const float2 ts = t2[2 * is];
+#pragma unroll
+                    for (int j = 0; j < KM; ++j)
+                        acc[j] = mh_seed_key(mh_vadd(mh_vmul(ts.x, DX[j]), mh_vmul(ts.y, DY[j])), is >> 2);
+                    for (int t = 0; t < ntp;) {
+#pragma unroll
+                        for (int u = 0; u < GRP; ++u) gb[u] = t2[2 * (t + GRP + u)];
+                        if constexpr (KM > 0) mh_key_blockm4<KM, KN, false>(acc, kk, ga, DX, DY, t >> 2);
+                        t += GRP;
+                        if (t >= ntp) {   // an odd number of blocks: the last one folds alone
+#pragma unroll
+                            for (int j = 0; j < KM; ++j) acc[j] = min(acc[j], kk[j]);
+                            break;
+                        }
+#pragma unroll
+                        for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * (t + GRP + u)];
+                        if constexpr (KM > 0) mh_key_blockm4<KM, KN, true>(acc, kk, gb, DX, DY, t >> 2);
+                        t += GRP;
+                    }
+                }
+                // decode: one compare for "any key past the valid range"; m = the key's upper bits with the constant 0b0011
+                // back in front (v_alignbit), loss = m - 2^-14.  The winning TAP: the lane reads its winning block's four
+                // (tx, ty) again, makes the four t' again -- the same instructions on the same operands, the same bits --
+                // and takes the first that equals m (three of them: if none is, it is the fourth); then that tap's confidence from its record.  (A seed that wins under
+                // the number of a block the walk did not reach, c = 1 mod 4, is that block's first tap: what lies behind
+                // it in LDS is read and never chosen.)
+                unsigned worst = acc[0];
+#pragma unroll
+                for (int j = 1; j < KM; ++j) worst = max(worst, acc[j]);
+                const bool bad = worst >= MH_KEY_BAD;
+                typedef const __attribute__((address_space(3))) mh_v2f *lds_f2;
+                typedef const __attribute__((address_space(3))) float *lds_f1;
+                // (two items at a time, a scheduling barrier between the pairs: all four at once hold 24 registers of taps)
+#pragma unroll
+                for (int j0 = 0; j0 < KM; j0 += 2) {
+                    if (j0) __builtin_amdgcn_sched_barrier(0);
+                    unsigned ad[2], mb[2];
+                    mh_v2f w[2][3];
+#pragma unroll
+                    for (int j = j0; j < KM && j < j0 + 2; ++j) {
+                        ad[j - j0] = rec1 + ((acc[j] & 15u) << 6);
+                        mb[j - j0] = __builtin_amdgcn_alignbit(3u, acc[j], 4u);
+#pragma unroll
+                        for (int u = 0; u < 3; ++u) w[j - j0][u] = *reinterpret_cast<lds_f2>((size_t)(ad[j - j0] + 16u * u));
+                    }
+#pragma unroll
+                    for (int j = j0; j < KM && j < j0 + 2; ++j) {
+                        unsigned off = 56u;   // (the fourth tap, where none of the three in front of it is the one)
+#pragma unroll
+                        for (int u = 2; u >= 0; --u) {
+                            const mh_v2f tp = w[j - j0][u];
+                            const float tq = mh_key_tprime(mh_vadd(mh_vmul(tp.x, DX[j]), mh_vmul(tp.y, DY[j])));
+                            off = (__float_as_uint(tq) == mb[j - j0]) ? 8u + 16u * u : off;
+                        }
+                        BC[j] = *reinterpret_cast<lds_f1>((size_t)(ad[j - j0] + off));
+                        ML[j] = __uint_as_float(mb[j - j0]) - MH_KEY_E;
+                    }
+                }
+                again = __ballot(bad) != 0ull;
+                if (again) MH_KEY_COUNT_ALWAYS(2);
+              }
+            } else if (!again) {
+                // patch 9 and 11: the per-tap keys
                 const int ntp = mh_key_walked<BIGP>(ntap);
                 // even taps of a 64-tap group into ke, odd taps into ko, the key's index = the tap's place among them
                 unsigned ke[KN], ko[KN];
@@ -764,21 +858,8 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                     float2 ga[GRP], gb[GRP];
 #pragma unroll
                     for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * (ta + u)];
-                    if constexpr (BIGP || KM == 0) {
 #pragma unroll
-                        for (int j = 0; j < KN; ++j) ke[j] = ko[j] = 0xFFFFFFFFu;
-                    } else {
-                        // the list's last tap seeds the accumulator of its parity (uniform), the other one starts empty
-                        const int is = ntap - 1;
-                        const float2 ts = t2[2 * is];
-                        const bool even = (is & 1) == 0;
-#pragma unroll
-                        for (int j = 0; j < KM; ++j) {
-                            const unsigned k = mh_tap_key(mh_vadd(mh_vmul(ts.x, DX[j]), mh_vmul(ts.y, DY[j])), is >> 1);
-                            ke[j] = even ? k : 0xFFFFFFFFu;
-                            ko[j] = even ? 0xFFFFFFFFu : k;
-                        }
-                    }
+                    for (int j = 0; j < KN; ++j) ke[j] = ko[j] = 0xFFFFFFFFu;
                     for (int t = ta; t < tb;) {
 #pragma unroll
                         for (int u = 0; u < GRP; ++u) gb[u] = t2[2 * (t + GRP + u)];
@@ -805,23 +886,19 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                         badr[j] = take ? ad : badr[j];
                     }
                 };
-                if constexpr (!BIGP) {   // patch <= 8x8: every list is one 64-tap group
-                    group(0, ntp);
-                    winner(0, true);
-                } else {                 // patch 9 and 11: up to two groups (a later group wins only on a strictly smaller loss)
-                    group(0, ntp < 64 ? ntp : 64);
-                    winner(0, true);
-                    for (int ta = 64; ta < ntp; ta += 64) {
-                        group(ta, ntp < ta + 64 ? ntp : ta + 64);
-                        winner(ta, false);
-                    }
+                // patch 9 and 11: up to two groups (a later group wins only on a strictly smaller loss)
+                group(0, ntp < 64 ? ntp : 64);
+                winner(0, true);
+                for (int ta = 64; ta < ntp; ta += 64) {
+                    group(ta, ntp < ta + 64 ? ntp : ta + 64);
+                    winner(ta, false);
                 }
                 // decode: one compare for "any key past the valid range", loss = t' - 2^-14 from the key's upper bits
                 // (v_alignbit puts the constant 0b00111 back in front), confidence of the winning tap from its record
                 unsigned worst = best[0];
 #pragma unroll
                 for (int j = 1; j < KM; ++j) worst = max(worst, best[j]);
-                const bool bad = worst >= MH_KEY_BAD;
+                const bool bad = worst >= MH_KEY_BAD_TAP;
 #pragma unroll
                 for (int j = 0; j < KM; ++j) {
                     BC[j] = *reinterpret_cast<const __attribute__((address_space(3))) float *>((size_t)(badr[j] + 8u));

@@ -1,10 +1,17 @@
 #!/usr/bin/env python
-"""Writes monohair_amd/csrc/mh_key_blocks.h: mh_key_block4<NI, KN>, four taps x NI items of the search kernel's key body
-(monohair_amd/csrc/pmvo_search.hip, which includes the header) as one hand-ordered inline-asm block per NI = 4, 3, 2, 1.
+"""Writes monohair_amd/csrc/mh_key_blocks.h: four taps x NI items of the search kernel's key bodies
+(monohair_amd/csrc/pmvo_search.hip, which includes the header) as one hand-ordered inline-asm block per NI = 4, 3, 2, 1:
+mh_key_block4<NI, KN>, which keys every tap (lists of more than one 64-tap group), and mh_key_blockm4<NI, KN, FOLD>, which
+keys the block (one-group lists).
 
 Order inside a half (two taps of the same parity, items j = 0..NI-1): the instructions of one kind for all items, then the
 next kind, so that every result is used NI - 1 or more instructions after it is produced; the second tap's products are
 issued between the first tap's sum and subtraction.  Even taps g[0], g[2] fold into ke, odd taps g[1], g[3] into ko.
+
+mh_key_blockm4: the four t' = C - |cs| of an item as above (mul, mul, add, sub each, the same order and bits), their minimum
+on the raw bits (one v_min_u32 after the first two, one v_min3_u32 after the other two) and ONE key (m << 4) | block.
+FOLD = false leaves that key in kk; FOLD = true folds kk and its own key into acc with one v_min3_u32, so that a pair of
+blocks costs 7 half-rate instructions per item (2 x (min, min3, lshl_or) + min3) where the per-tap keys cost 12.
 
     python tools/gen_key_blocks.py > monohair_amd/csrc/mh_key_blocks.h
 
@@ -34,6 +41,79 @@ def block4(n):
     return lines
 
 
+WIDTH = 2   # items of a block-key block that are interleaved; the temporaries are those of WIDTH items
+
+
+def blockm4(n, fold, width=WIDTH):
+    lines = []
+    for j0 in range(0, n, width):
+        items = range(j0, min(n, j0 + width))
+
+        def add(fmt):   # j the item, s its set of temporaries; FOLD = false: the key is made in kk itself (d), the fourth one
+            for j in items: lines.append(fmt.format(j=j, s=j - j0, d=f"d{j - j0}" if fold else f"k{j}"))
+
+        add("v_mul_f32_e32 %[a{s}], %[t0x], %[x{j}]")
+        add("v_mul_f32_e32 %[b{s}], %[t0y], %[y{j}]")
+        add("v_mul_f32_e32 %[c{s}], %[t2x], %[x{j}]")
+        add("v_add_f32_e32 %[a{s}], %[a{s}], %[b{s}]")
+        add("v_mul_f32_e32 %[b{s}], %[t2y], %[y{j}]")
+        add("v_sub_f32_e64 %[a{s}], %[cc], |%[a{s}]|")
+        add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+        add("v_mul_f32_e32 %[{d}], %[t1x], %[x{j}]")
+        add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
+        add("v_mul_f32_e32 %[b{s}], %[t1y], %[y{j}]")
+        add("v_min_u32_e32 %[a{s}], %[a{s}], %[c{s}]")
+        add("v_mul_f32_e32 %[c{s}], %[t3x], %[x{j}]")
+        add("v_add_f32_e32 %[{d}], %[{d}], %[b{s}]")
+        add("v_mul_f32_e32 %[b{s}], %[t3y], %[y{j}]")
+        add("v_sub_f32_e64 %[{d}], %[cc], |%[{d}]|")
+        add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+        add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
+        add("v_min3_u32 %[a{s}], %[a{s}], %[{d}], %[c{s}]")
+        if fold:
+            add("v_lshl_or_b32 %[a{s}], %[a{s}], 4, %[ib]")
+            add("v_min3_u32 %[m{j}], %[m{j}], %[k{j}], %[a{s}]")
+        else:
+            add("v_lshl_or_b32 %[k{j}], %[a{s}], 4, %[ib]")
+    return lines
+
+
+def emitm(n, fold, width=WIDTH, name=None):
+    lines = blockm4(n, fold, width)
+    w = min(n, width)
+    body = "\n".join('                "%s%s"' % (l, "\\n\\t" if i < len(lines) - 1 else "") for i, l in enumerate(lines))
+    if fold:
+        outs = ([f'[m{j}] "+v"(acc[{j}])' for j in range(n)] + [f'[{c}{s}] "=&v"({c}[{s}])' for c in "abcd" for s in range(w)])
+        kin = [f'[k{j}] "v"(kk[{j}])' for j in range(n)]
+    else:
+        outs = ([f'[k{j}] "=&v"(kk[{j}])' for j in range(n)] + [f'[{c}{s}] "=&v"({c}[{s}])' for c in "abc" for s in range(w)])
+        kin = []
+    ins = ", ".join([f'[t{u}x] "v"(g[{u}].x), [t{u}y] "v"(g[{u}].y)' for u in range(4)] +
+                    [f'[x{j}] "v"(DX[{j}]), [y{j}] "v"(DY[{j}])' for j in range(n)] + kin +
+                    ['[cc] "s"(MH_KEY_C)', '[ib] "s"(ib)'])
+    head = "if" if fold else "else"
+    cond = " constexpr (FOLD)" if fold else ""
+    return (f"        {head}{cond} {{\n            asm volatile(\n{body}\n                : {', '.join(outs)}\n                : {ins}\n"
+            f'                : "memory");\n        }}\n')
+
+
+def emitm_n(n, width=WIDTH):
+    head = "if" if n == 4 else "else if"
+    return f"    {head} constexpr (NI == {n}) {{\n" + emitm(n, True, width) + emitm(n, False, width) + "    }\n"
+
+
+HEADM = """
+// the block-key body: ib = the block's number in its list (0..15)
+template <int NI, int KN, bool FOLD>
+__device__ __forceinline__ void mh_key_blockm4(unsigned (&acc)[KN], unsigned (&kk)[KN], const float2 (&g)[4],
+                                               const float (&DX)[KN], const float (&DY)[KN], int ib) {
+    static_assert(NI >= 1 && NI <= 4 && NI <= KN, "mh_key_blockm4: 1..4 items");
+    constexpr int NW = NI < %d ? NI : %d;
+    float a[NW], b[NW], c[NW];
+    [[maybe_unused]] float d[NW];
+"""
+
+
 def emit(n):
     lines = block4(n)
     body = "\n".join('            "%s%s"' % (l, "\\n\\t" if i < len(lines) - 1 else "") for i, l in enumerate(lines))
@@ -56,9 +136,12 @@ __device__ __forceinline__ void mh_key_block4(unsigned (&ke)[KN], unsigned (&ko)
 """
 
 
-def header():
-    return HEAD + "".join(emit(n) for n in (4, 3, 2, 1)) + "}\n"
+def header(width=WIDTH):
+    return (HEAD + "".join(emit(n) for n in (4, 3, 2, 1)) + "}\n" +
+            HEADM % (width, width) + "".join(emitm_n(n, width) for n in (4, 3, 2, 1)) + "}\n")
 
 
 if __name__ == "__main__":
-    print(header(), end="")
+    import sys
+    # --width W: another interleave of mh_key_blockm4, for tools/ubench/key_block_forms.hip (the committed header is WIDTH)
+    print(header(int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--width" else WIDTH), end="")
