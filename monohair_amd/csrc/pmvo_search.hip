@@ -13,7 +13,7 @@
 // groups) and the inner loop is pure VALU: per (item, tap) 2 mul + add + (1-|x|) + cmp + 2 cndmask in the portable kernel and
 // the select body of the shipped one; its key body keeps the running (loss, tap) minimum as one integer key per item and
 // needs 2 mul + add + sub + lshl_or + half a min3 (see MH_KEY_C) -- for patches up to 8 x 8 the key is that of a four-tap
-// block, 2 mul + add + sub per tap and min, min3, lshl_or + half a min3 per block (see mh_seed_key); a list's last tap
+// block, 2 mul + add per tap and max, max3, sub, lshl_or + half a min3 per block (see MH_KEY_C, mh_seed_key); a list's last tap
 // seeds the minimum instead of padding a four-tap block (see mh_key_walked).
 // Views in which the point is not visible (vis == -1 => weight 0, PMVO.py:212) are skipped: adding
 // their exact zeros would not change any sum.
@@ -317,13 +317,23 @@ __device__ __forceinline__ void mh_tap_update(float (&ML)[KA], float (&BC)[KA], 
 // add, sub, lshl_or per evaluation + half a min3: 5.5 instructions instead of 7, two accumulators per item, one compare
 // and two selects per (item, view) to merge them.
 // The one-group kernels (patch <= 8 x 8: !BIGP) key the four-tap BLOCK instead of the tap (mh_key_blockm4): the tap's place is
-// wanted once per (item, view), for the winner, and lshl_or and min3 issue at half the rate of mul / add / sub.  The four t' of
-// a block as above, m = their minimum on the raw bits (positive floats: monotone), key = (m << 4) | block (16 blocks of a
-// 64-tap group; the top bit of the key, the last of the constant 0b00111, stays set), ONE accumulator per item, the key of a
-// block kept until the next block folds both with one v_min3_u32: per block and item 16 full-rate + min, min3, lshl_or + half
-// a min3 = 3.5 half-rate instructions instead of 6.  An earlier block wins a tie in m by its smaller number.  After the walk
-// the lane reads the taps of ITS winning block again (per-lane LDS addresses), makes their t' again -- the same instructions
-// on the same operands -- and takes the first that equals m: the lexicographic minimum of (loss, tap) as before.
+// wanted once per (item, view), for the winner, and lshl_or, min3 and max3 issue at half the rate of mul / add / sub.  m = the
+// minimum of the block's four t', key = (m << 4) | block (16 blocks of a 64-tap group; the top bit of the key, the last of the
+// constant 0b00111, stays set), ONE accumulator per item, the key of a block kept until the next block folds both with one
+// v_min3_u32.  An earlier block wins a tie in m by its smaller number.
+// The block does not make four t': fl(C - x) is monotone non-increasing in x = |cs| and rounding keeps that order, so
+//   min over the block's taps of fl(C - |cs_t|) == fl(C - max over the taps of |cs_t|)
+// bit for bit, for every input.  The four cs as above (mul, mul, add each, the same order and bits), their maximum of |cs| with
+// v_max_f32 (taps 0 and 2) and v_max3_f32 (taps 1 and 3), |.| as source modifiers, and ONE v_sub_f32: per block and item 13
+// full-rate + max, max3, lshl_or + half a min3 = 3.5 half-rate instructions (16 + 3.5 with four subtractions and v_min_u32 /
+// v_min3_u32 on the raw bits, tools/gen_key_blocks.py --form sub4; 16 + 6 with per-tap keys).  NaN: a NaN cs comes out of
+// v_add_f32, so it is quiet, and v_max_f32 / v_max3_f32 return the other operand(s): the tap is ignored, as the raw bits of a
+// NaN t' above every valid t' ignored it; four NaN taps give a NaN maximum, a NaN t' and a key >= MH_KEY_BAD, which matters
+// only where it is the list's minimum.  (0, 0) records give |cs| = 0, which never raises a maximum; a block of them gives
+// t' = C.  A denormal x gives C whether or not it is flushed.
+// After the walk the lane reads the taps of ITS winning block again (per-lane LDS addresses), makes the t' of each -- the
+// instructions of mh_key_tprime on the same operands -- and takes the first that equals m: the lexicographic minimum of
+// (loss, tap) as before; two taps of different |cs| and the same loss are decided there, on t', not on |cs|.
 // What the key cannot state -- a winner with x <= 2^-14 (t' >= 1 lands on the coarser grid of [1, 2)), a NaN -- shows as
 // key >= MH_KEY_BAD (MH_KEY_BAD_TAP for the per-tap keys); a wave that sees one on any of its lanes evaluates that view again with the compare-and-select body
 // (mh_tap_update), which is also what runs for one-tap lists and for a NaN seed tap.  Both bodies give the same bits
@@ -394,8 +404,10 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
 }
 
 // Four taps x NI items of the per-tap key body as ONE hand-ordered block (mh_key_block4; the block-key body's mh_key_blockm4 is
-// made the same way, two items at a time: with four the headline kernel spills): per item 16 full-rate (mul, mul, add, sub) + 4 v_lshl_or +
-// 2 v_min3 (88 instructions for four items), every result used at least NI - 1 instructions after it is produced.  (Left to
+// made the same way, two items at a time: with four the headline kernel spills -- per item 13 full-rate + max, max3, lshl_or and
+// a min3 in every second block, no result of a pair of items read by the next instruction; see MH_KEY_C): per item 16 full-rate
+// (mul, mul, add, sub) + 4 v_lshl_or + 2 v_min3 (88 instructions for four items), every result used at least NI - 1
+// instructions after it is produced.  (Left to
 // the compiler as one asm statement per instruction, its hazard recogniser pads every inline-asm result that is read by
 // the very next instruction with an s_nop -- it cannot see that no dst_sel is involved: ~9 per block.)  The "memory"
 // clobber keeps the LDS reads of the NEXT tap group, issued in front of the block, in front of it.

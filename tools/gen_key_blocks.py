@@ -8,12 +8,19 @@ Order inside a half (two taps of the same parity, items j = 0..NI-1): the instru
 next kind, so that every result is used NI - 1 or more instructions after it is produced; the second tap's products are
 issued between the first tap's sum and subtraction.  Even taps g[0], g[2] fold into ke, odd taps g[1], g[3] into ko.
 
-mh_key_blockm4: the four t' = C - |cs| of an item as above (mul, mul, add, sub each, the same order and bits), their minimum
-on the raw bits (one v_min_u32 after the first two, one v_min3_u32 after the other two) and ONE key (m << 4) | block.
-FOLD = false leaves that key in kk; FOLD = true folds kk and its own key into acc with one v_min3_u32, so that a pair of
-blocks costs 7 half-rate instructions per item (2 x (min, min3, lshl_or) + min3) where the per-tap keys cost 12.
+mh_key_blockm4: the four cs of an item as above (mul, mul, add each, the same order and bits), m = the minimum of the four
+t' = fl(C - |cs|), and ONE key (m << 4) | block.  FORM "max" (the committed header): fl(C - x) is monotone non-increasing in x,
+so m = fl(C - max |cs|) bit for bit -- v_max_f32 of |cs| of taps 0 and 2, v_max3_f32 with taps 1 and 3 (|.| as source
+modifiers; a NaN operand is dropped, as its raw bits lost every minimum), one v_sub_f32: 13 full-rate instructions per item.
+FORM "sub4" (the form before, kept for tools/ubench/key_block_forms.hip): four subtractions, the minimum on the raw bits with
+one v_min_u32 and one v_min3_u32: 16 full-rate instructions.  Both: two items interleaved line by line, so that no result of a
+pair is read by the next instruction (the lone third item of NI = 3 and NI = 1 cannot avoid it: the sum of a tap follows its
+second product, and the tail max3, sub, lshl_or, min3 is one chain), four temporaries per item, kk the fourth where FOLD = false.
+FOLD = false leaves the key in kk; FOLD = true folds kk and its own key into acc with one v_min3_u32, so that a pair of
+blocks costs 7 half-rate instructions per item (2 x (max, max3, lshl_or) + min3) where the per-tap keys cost 12.
 
     python tools/gen_key_blocks.py > monohair_amd/csrc/mh_key_blocks.h
+    python tools/gen_key_blocks.py --form sub4 --only-blockm4 --name mh_key_blockm4_sub4 > sub4.h     # beside it, for the micro-benchmark
 
 tests/test_host.py compares the committed header with header() below.
 """
@@ -42,9 +49,10 @@ def block4(n):
 
 
 WIDTH = 2   # items of a block-key block that are interleaved; the temporaries are those of WIDTH items
+FORM = "max"   # "max": max of the four |cs|, one subtraction (the committed header); "sub4": four t', their minimum (the form before)
 
 
-def blockm4(n, fold, width=WIDTH):
+def blockm4(n, fold, width=WIDTH, form=FORM):
     lines = []
     for j0 in range(0, n, width):
         items = range(j0, min(n, j0 + width))
@@ -57,19 +65,31 @@ def blockm4(n, fold, width=WIDTH):
         add("v_mul_f32_e32 %[c{s}], %[t2x], %[x{j}]")
         add("v_add_f32_e32 %[a{s}], %[a{s}], %[b{s}]")
         add("v_mul_f32_e32 %[b{s}], %[t2y], %[y{j}]")
-        add("v_sub_f32_e64 %[a{s}], %[cc], |%[a{s}]|")
-        add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
-        add("v_mul_f32_e32 %[{d}], %[t1x], %[x{j}]")
-        add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
-        add("v_mul_f32_e32 %[b{s}], %[t1y], %[y{j}]")
-        add("v_min_u32_e32 %[a{s}], %[a{s}], %[c{s}]")
-        add("v_mul_f32_e32 %[c{s}], %[t3x], %[x{j}]")
-        add("v_add_f32_e32 %[{d}], %[{d}], %[b{s}]")
-        add("v_mul_f32_e32 %[b{s}], %[t3y], %[y{j}]")
-        add("v_sub_f32_e64 %[{d}], %[cc], |%[{d}]|")
-        add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
-        add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
-        add("v_min3_u32 %[a{s}], %[a{s}], %[{d}], %[c{s}]")
+        if form == "sub4":   # t' of every tap, the minimum on their raw bits
+            add("v_sub_f32_e64 %[a{s}], %[cc], |%[a{s}]|")
+            add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+            add("v_mul_f32_e32 %[{d}], %[t1x], %[x{j}]")
+            add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
+            add("v_mul_f32_e32 %[b{s}], %[t1y], %[y{j}]")
+            add("v_min_u32_e32 %[a{s}], %[a{s}], %[c{s}]")
+            add("v_mul_f32_e32 %[c{s}], %[t3x], %[x{j}]")
+            add("v_add_f32_e32 %[{d}], %[{d}], %[b{s}]")
+            add("v_mul_f32_e32 %[b{s}], %[t3y], %[y{j}]")
+            add("v_sub_f32_e64 %[{d}], %[cc], |%[{d}]|")
+            add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+            add("v_sub_f32_e64 %[c{s}], %[cc], |%[c{s}]|")
+            add("v_min3_u32 %[a{s}], %[a{s}], %[{d}], %[c{s}]")
+        else:                # "max": the maximum of the four |cs| first, ONE t' = C - that
+            add("v_mul_f32_e32 %[{d}], %[t1x], %[x{j}]")
+            add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+            add("v_mul_f32_e32 %[b{s}], %[t1y], %[y{j}]")
+            add("v_max_f32_e64 %[a{s}], |%[a{s}]|, |%[c{s}]|")
+            add("v_mul_f32_e32 %[c{s}], %[t3x], %[x{j}]")
+            add("v_add_f32_e32 %[{d}], %[{d}], %[b{s}]")
+            add("v_mul_f32_e32 %[b{s}], %[t3y], %[y{j}]")
+            add("v_add_f32_e32 %[c{s}], %[c{s}], %[b{s}]")
+            add("v_max3_f32 %[a{s}], %[a{s}], |%[{d}]|, |%[c{s}]|")
+            add("v_sub_f32_e32 %[a{s}], %[cc], %[a{s}]")
         if fold:
             add("v_lshl_or_b32 %[a{s}], %[a{s}], 4, %[ib]")
             add("v_min3_u32 %[m{j}], %[m{j}], %[k{j}], %[a{s}]")
@@ -78,8 +98,8 @@ def blockm4(n, fold, width=WIDTH):
     return lines
 
 
-def emitm(n, fold, width=WIDTH, name=None):
-    lines = blockm4(n, fold, width)
+def emitm(n, fold, width=WIDTH, form=FORM):
+    lines = blockm4(n, fold, width, form)
     w = min(n, width)
     body = "\n".join('                "%s%s"' % (l, "\\n\\t" if i < len(lines) - 1 else "") for i, l in enumerate(lines))
     if fold:
@@ -97,9 +117,9 @@ def emitm(n, fold, width=WIDTH, name=None):
             f'                : "memory");\n        }}\n')
 
 
-def emitm_n(n, width=WIDTH):
+def emitm_n(n, width=WIDTH, form=FORM):
     head = "if" if n == 4 else "else if"
-    return f"    {head} constexpr (NI == {n}) {{\n" + emitm(n, True, width) + emitm(n, False, width) + "    }\n"
+    return f"    {head} constexpr (NI == {n}) {{\n" + emitm(n, True, width, form) + emitm(n, False, width, form) + "    }\n"
 
 
 HEADM = """
@@ -136,12 +156,22 @@ __device__ __forceinline__ void mh_key_block4(unsigned (&ke)[KN], unsigned (&ko)
 """
 
 
-def header(width=WIDTH):
+def header(width=WIDTH, form=FORM):
     return (HEAD + "".join(emit(n) for n in (4, 3, 2, 1)) + "}\n" +
-            HEADM % (width, width) + "".join(emitm_n(n, width) for n in (4, 3, 2, 1)) + "}\n")
+            HEADM % (width, width) + "".join(emitm_n(n, width, form) for n in (4, 3, 2, 1)) + "}\n")
 
 
 if __name__ == "__main__":
-    import sys
-    # --width W: another interleave of mh_key_blockm4, for tools/ubench/key_block_forms.hip (the committed header is WIDTH)
-    print(header(int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--width" else WIDTH), end="")
+    import argparse
+    # --width W: another interleave of mh_key_blockm4; --form sub4: the four-subtraction block; --name N: the function under another
+    # name, so that tools/ubench/key_block_forms.hip can hold both forms (the committed header is WIDTH, FORM, mh_key_blockm4)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=WIDTH)
+    ap.add_argument("--form", choices=("max", "sub4"), default=FORM)
+    ap.add_argument("--name", default="mh_key_blockm4")
+    ap.add_argument("--only-blockm4", action="store_true", help="leave mh_key_block4 out (a second include beside the header)")
+    args = ap.parse_args()
+    text = header(args.width, args.form)
+    if args.only_blockm4:
+        text = text[text.index(HEADM[:40]):]
+    print(text.replace("mh_key_blockm4", args.name), end="")

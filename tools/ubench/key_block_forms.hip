@@ -1,19 +1,24 @@
 // Micro-benchmark (gfx950): one (wave, view) visit of the one-group key kernels of csrc/pmvo_search.hip -- a 49-tap list (7 x 7 patch)
-// in LDS, FOUR items per lane: the seeded last tap, twelve four-tap blocks, the decode -- in two forms, both on the blocks of
-// csrc/mh_key_blocks.h itself:
+// in LDS, FOUR items per lane: the seeded last tap, twelve four-tap blocks, the decode -- in three forms, on the blocks of
+// csrc/mh_key_blocks.h itself and of tools/gen_key_blocks.py --form sub4:
 //   T  the per-TAP keys: key = (t' << 5) | place, even taps into one accumulator and odd taps into another (mh_key_block4), the two
 //      merged after the walk, the winner's confidence read from its record
-//   M  the per-BLOCK keys: m = min of the block's four t', key = (m << 4) | block, one accumulator (mh_key_blockm4); after the walk
-//      every lane reads ITS winning block's (tx, ty) again, makes the t' again and takes the first that equals m
+//   M  the per-BLOCK keys: m = min of the block's four t', key = (m << 4) | block, one accumulator (the block of --form sub4: four
+//      subtractions, v_min_u32, v_min3_u32); after the walk every lane reads ITS winning block's (tx, ty) again, makes the t' again
+//      and takes the first that equals m
+//   X  the same with the MAXIMUM first: m = C - max of the block's four |cs| (mh_key_blockm4 as committed: v_max_f32, v_max3_f32
+//      with |.| on the sources, one subtraction); the rest is M's
 // The taps are unit vectors at the angles pi * t / 49, the items' directions are spread over the half circle lane by lane, so that the
 // winning blocks differ among the lanes of a wave (the per-lane LDS reads of M go to twelve or more different blocks; printed).  Both
-// forms add loss * confidence and confidence over the visits; the sums are compared bit for bit.
+// forms add loss * confidence and confidence over the visits; the sums are compared bit for bit (T with M, M with X).
 // 5 waves per SIMD (1280 workgroups of 256 lanes).  ALONE: every wave visits, back to back.  ALTERNATING: every wave projects its four
 // items (the plain chains of tools/ubench/proj_forms.hip, form S) and then visits, the workgroups starting 0, 2, 4, 7 and 9 blocks into
 // that cycle, so that a wave in its decode runs beside waves in their key blocks and in their projection.
 // Prints SIMD time per (wave, view) visit = launch time / visits / 5 waves, in ns and in cycles at an assumed 2.4 GHz: median and spread
 // (max - min) of REPS launches behind WARM that warm up.
-//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -o /tmp/key_block_forms tools/ubench/key_block_forms.hip
+//   python tools/gen_key_blocks.py --form sub4 --only-blockm4 --name mh_key_blockm4_sub4 > /tmp/sub4.h
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -DKEY_BLOCKS_SUB4_H='"/tmp/sub4.h"' \
+//         -o /tmp/key_block_forms tools/ubench/key_block_forms.hip
 // Another interleave of mh_key_blockm4 (tools/gen_key_blocks.py --width W > /tmp/w.h): add -DKEY_BLOCKS_H='"/tmp/w.h"'.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -28,6 +33,10 @@
 #define KEY_BLOCKS_H "../../monohair_amd/csrc/mh_key_blocks.h"
 #endif
 #include KEY_BLOCKS_H
+#ifndef KEY_BLOCKS_SUB4_H
+#error "KEY_BLOCKS_SUB4_H: the header of tools/gen_key_blocks.py --form sub4 --only-blockm4 --name mh_key_blockm4_sub4"
+#endif
+#include KEY_BLOCKS_SUB4_H
 
 #define WGS 1280     // 256 CUs x 5 workgroups: 5 waves on every SIMD
 #define NTAP 49
@@ -140,7 +149,8 @@ DEV void visit_T(const float4 *rec, int nblk, const float (&DX)[4], const float 
     }
 }
 
-// ---- one visit, form M; blk[j] = the winning block of item j
+// ---- one visit, form M (MAXF = false) or X (MAXF = true); blk[j] = the winning block of item j
+template <bool MAXF>
 DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float (&DY)[4], float (&ML)[4], float (&BC)[4], unsigned (&blk)[4]) {
     const int ntp = 4 * nblk;
     unsigned acc[4], kk[4];
@@ -156,7 +166,8 @@ DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float 
     for (int t = 0; t < ntp;) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) gb[u] = t2[2 * (t + 4 + u)];
-        mh_key_blockm4<4, 4, false>(acc, kk, ga, DX, DY, t >> 2);
+        if constexpr (MAXF) mh_key_blockm4<4, 4, false>(acc, kk, ga, DX, DY, t >> 2);
+        else mh_key_blockm4_sub4<4, 4, false>(acc, kk, ga, DX, DY, t >> 2);
         t += 4;
         if (t >= ntp) {
 #pragma unroll
@@ -165,7 +176,8 @@ DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float 
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) ga[u] = t2[2 * (t + 4 + u)];
-        mh_key_blockm4<4, 4, true>(acc, kk, gb, DX, DY, t >> 2);
+        if constexpr (MAXF) mh_key_blockm4<4, 4, true>(acc, kk, gb, DX, DY, t >> 2);
+        else mh_key_blockm4_sub4<4, 4, true>(acc, kk, gb, DX, DY, t >> 2);
         t += 4;
     }
 #pragma unroll
@@ -196,7 +208,7 @@ DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float 
     }
 }
 
-// FORM 0 T, 1 M.  PROJ: every visit is preceded by the projection of the wave's four items.
+// FORM 0 T, 1 M, 2 X.  PROJ: every visit is preceded by the projection of the wave's four items.
 template <int FORM, bool PROJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 visit_kernel(const float *__restrict__ cams, const float4 *__restrict__ list /* [1 + NTAP + 7] */, int visits,
@@ -234,7 +246,7 @@ visit_kernel(const float *__restrict__ cams, const float4 *__restrict__ list /* 
         float ML[4], BC[4];
         const int nblk = (ahead && i == 0) ? ahead : 12;   // (the first, short walk only staggers the workgroups)
         if constexpr (FORM == 0) visit_T(s_taps, nblk, DX, DY, ML, BC);
-        else visit_M(s_taps, nblk, DX, DY, ML, BC, blk);
+        else visit_M<FORM == 2>(s_taps, nblk, DX, DY, ML, BC, blk);
         if (!(ahead && i == 0)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -328,32 +340,39 @@ int main() {
     const int visits = 2000;
     printf("wall clock %d kHz; %d workgroups x 256 lanes, 5 waves per SIMD; %d visits of 4 items x (seed + 12 blocks + decode) per wave; %d launches each\n",
            rate_khz, WGS, visits, REPS);
-    double med[2][2], spr[2][2];
-    std::vector<float> sums[2][2];
-    std::vector<unsigned> blocks[2][2];
+    double med[2][3], spr[2][3];
+    std::vector<float> sums[2][3];
+    std::vector<unsigned> blocks[2][3];
     if (run<0, false>(d, visits, tick_ns, med[0][0], spr[0][0], sums[0][0], blocks[0][0])) return 1;
     if (run<1, false>(d, visits, tick_ns, med[0][1], spr[0][1], sums[0][1], blocks[0][1])) return 1;
+    if (run<2, false>(d, visits, tick_ns, med[0][2], spr[0][2], sums[0][2], blocks[0][2])) return 1;
     if (run<0, true>(d, visits, tick_ns, med[1][0], spr[1][0], sums[1][0], blocks[1][0])) return 1;
     if (run<1, true>(d, visits, tick_ns, med[1][1], spr[1][1], sums[1][1], blocks[1][1])) return 1;
-    const char *mode[2] = {"ALONE      ", "ALTERNATING"}, *form[2] = {"T per-tap keys  ", "M per-block keys"};
+    if (run<2, true>(d, visits, tick_ns, med[1][2], spr[1][2], sums[1][2], blocks[1][2])) return 1;
+    const char *mode[2] = {"ALONE      ", "ALTERNATING"}, *form[3] = {"T per-tap keys  ", "M per-block keys", "X maximum first "};
+    const char *nm = "TMX";
     for (int p = 0; p < 2; ++p)
-        for (int f = 0; f < 2; ++f)
+        for (int f = 0; f < 3; ++f)
             printf("%s %s per (wave, view) visit%s: SIMD %7.2f ns = %6.1f cycles@2.4GHz, spread %.2f ns\n", mode[p], form[f],
                    p ? " with its projection" : "", med[p][f], med[p][f] * 2.4, spr[p][f]);
-    for (int p = 0; p < 2; ++p) {
-        const double gain = med[p][0] - med[p][1], noise = std::max(spr[p][0], spr[p][1]);
-        printf("%s M is %+.2f ns = %+.1f cycles (%+.1f %%) against T; larger spread %.2f ns: %s\n", mode[p], -gain, -gain * 2.4, -100.0 * gain / med[p][0],
-               noise, gain > noise ? "cheaper by more than the spread" : "NOT cheaper by more than the spread");
-    }
+    for (int p = 0; p < 2; ++p)
+        for (int f = 1; f < 3; ++f) {   // M against T, X against M
+            const double gain = med[p][f - 1] - med[p][f], noise = std::max(spr[p][f - 1], spr[p][f]);
+            printf("%s %c is %+.2f ns = %+.1f cycles (%+.1f %%) against %c; larger spread %.2f ns: %s\n", mode[p], nm[f], -gain, -gain * 2.4,
+                   -100.0 * gain / med[p][f - 1], nm[f - 1], noise, gain > noise ? "cheaper by more than the spread" : "NOT cheaper by more than the spread");
+        }
     bool same = true;
-    for (int p = 0; p < 2; ++p) same = same && memcmp(sums[p][0].data(), sums[p][1].data(), sizeof(float) * sums[p][0].size()) == 0;
+    for (int p = 0; p < 2; ++p)
+        for (int f = 1; f < 3; ++f) same = same && memcmp(sums[p][0].data(), sums[p][f].data(), sizeof(float) * sums[p][0].size()) == 0;
+    bool same_blocks = true;
+    for (int p = 0; p < 2; ++p) same_blocks = same_blocks && blocks[p][1] == blocks[p][2];
     int distinct = 0;
     {
         bool seen[16] = {};
         for (int l = 0; l < 64; ++l) seen[blocks[0][1][l * 4] & 15u] = true;   // item 0 of the lanes of wave 0
         for (int i = 0; i < 16; ++i) distinct += seen[i] ? 1 : 0;
     }
-    printf("sums of loss * confidence and of confidence, 1024 items of workgroup 0: T and M %s; winning blocks of item 0 among the 64 lanes of wave 0: %d different\n",
-           same ? "bit-equal" : "DIFFER", distinct);
-    return same ? 0 : 2;
+    printf("sums of loss * confidence and of confidence, 1024 items of workgroup 0: T, M and X %s; winning blocks of M and X %s; winning blocks of item 0 among the 64 lanes of wave 0: %d different\n",
+           same ? "bit-equal" : "DIFFER", same_blocks ? "equal" : "DIFFER", distinct);
+    return same && same_blocks ? 0 : 2;
 }
