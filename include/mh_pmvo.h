@@ -622,6 +622,56 @@ int mh_photo_view(mh_ctx *ctx, const float *cam_host, const float *points, const
                   int width, const float *depth0, int bust_code, int background_code, void *scratch, size_t scratch_bytes,
                   uint8_t *gray_u8, int32_t *cover, void *stream);
 
+/* Capture agreement (monohair_amd.hairreproj; no counterpart in the reference): a strand set scored against the observed 2D
+ * maps of the capture it was reconstructed from -- do the strands run where the cameras saw hair, and along the orientation
+ * they saw? -- a measurement that needs no ground truth.  Per view the inputs are the camera record, the observed planes
+ * ori_u8 / conf_u8 / mask_u8 (uint8 [H,W] file codes, what mh_ctx_set_view_u8 takes), an optional occluder plane depth0
+ * (float32 [H,W], PMVO's depth convention, background 255) and the strand set: points [n_points,3] float32 WORLD points,
+ * offsets [n_strands+1] (int64).  The rule, per view:
+ *
+ * Vertex, segment, sample.  Exactly those of "Hair capture": mh_capture_project's (row, col, z255, valid); a segment = two
+ *   consecutive valid points of one strand, n = max(1, ceil(max(|dr|, |dc|))), dropped and counted when n > 8192; qc =
+ *   rint(4096*c2), qs = rint(4096*s2) and 0 when len = 0; sample j at t = (j + 0.5)/n with the half-to-even centre pixel p and
+ *   zf = float32(z255_a + t*dz).
+ * Front plane.  zmin = pass A of the capture rule (mh_capture_zmin) at a footprint `radius`, with depth0.
+ * Classes of a sample, judged at its centre pixel p alone.  A sample whose centre lies outside the image, or whose zf is not
+ *   finite, belongs to no class.
+ *     visible    zf <= depth0[p] (when depth0 is given) and zf <= zmin[p] + tol (a float32 addition)
+ *     on hair    visible and mask_u8[p] >= 52: PMVO's m > 0.2 on the loaders' decode (codes 50 and 51 decode to 50/255 and
+ *                51/255, which are not above 0.2: they are not hair)
+ *     confident  on hair and conf_u8[p] >= conf_min_code and ori_u8[p] < 180
+ *     agrees at bound k (k < n_bounds <= 8)  confident, the segment's len > 0, and qc*T[c][0] + qs*T[c][1] >= bound[k] in
+ *                float64 with c = ori_u8[p] (the two products rounded, then their sum); T = the float32 table of the capture
+ *                rule's resolve step, widened (HOST); bound[k] HOST float64 (the callers set 4096*cos(2*angle_k))
+ * Counters.  A row of 4 + n_bounds int64: {visible, on hair, confident, dropped segments, agrees[0], .. agrees[n_bounds-1]}:
+ *   the numbers of samples of each class, and of segments with n > 8192.  strand_counts [n_strands, 4 + n_bounds] holds one row
+ *   per strand, summed over its segments; it is ADDED to, never zeroed by a call, so one buffer collects all views.  view_counts
+ *   [4 + n_bounds] is the same row summed over all strands of this call (zeroed first).  Integer sums: the result does not
+ *   depend on the order of arrival.
+ * Silhouette, three int64 pixel counts from zmin and mask_u8 (zeroed first): {predicted and observed, predicted only, observed
+ *   only}; predicted = zmin[p] finite, observed = mask_u8[p] >= 52.
+ *
+ * mh_support_accumulate: vert / valid = mh_capture_project's, zmin = mh_capture_zmin's.  table_host: 180 x 2 float32 (HOST),
+ *   bounds_host: n_bounds float64 (HOST), 0 <= conf_min_code <= 256 (256: no pixel is confident).  depth0 may be NULL;
+ *   strand_counts may be NULL when n_points = 0.  No launch is made for fewer than two points.
+ * mh_support_silhouette: silhouette [3].
+ * mh_support_view: mh_capture_project, mh_capture_zmin and the two steps for one view on a scratch of
+ *   mh_support_scratch_bytes(n_points, H, W) bytes, whose first int32 is left holding pass A's dropped count.
+ *   0 <= radius <= 16, tol >= 0, H*W < 2^31, 1 <= n_bounds <= 8. */
+size_t mh_support_scratch_bytes(int n_points, int H, int W);
+int mh_support_accumulate(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets, int n_strands,
+                          int n_points, int H, int W, float tol, const float *depth0, const float *zmin,
+                          const uint8_t *ori_u8, const uint8_t *conf_u8, const uint8_t *mask_u8, int conf_min_code,
+                          const float *table_host, const double *bounds_host, int n_bounds, long long *strand_counts,
+                          long long *view_counts, void *stream);
+int mh_support_silhouette(mh_ctx *ctx, const float *zmin, const uint8_t *mask_u8, int H, int W, long long *silhouette,
+                          void *stream);
+int mh_support_view(mh_ctx *ctx, const float *cam_host, const float *points, const long long *offsets, int n_strands,
+                    int n_points, int H, int W, int radius, float tol, const float *depth0, const uint8_t *ori_u8,
+                    const uint8_t *conf_u8, const uint8_t *mask_u8, int conf_min_code, const float *table_host,
+                    const double *bounds_host, int n_bounds, void *scratch, size_t scratch_bytes, long long *strand_counts,
+                    long long *view_counts, long long *silhouette, void *stream);
+
 /* Strand volume (monohair_amd.hairvolume; no counterpart in the reference): a strand set turned into the volume the fit of
  * refine would ideally produce -- the occupied voxels with one direction each, in PMVO's own voxel conventions -- so that the
  * strand stage can be run on a perfect volume and a fitted volume can be scored.  points [n_points,3] float32 in `.hair`

@@ -90,6 +90,11 @@ _SIGS = {
     "mh_photo_resolve": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
     "mh_photo_view": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, ci, ci, ci, ci, vp, ci, ci, vp, csz, vp, vp,
                            vp]),
+    "mh_support_scratch_bytes": (csz, [ci, ci, ci]),
+    "mh_support_accumulate": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp]),
+    "mh_support_silhouette": (ci, [vp, vp, vp, ci, ci, vp, vp]),
+    "mh_support_view": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, ci, vp, vp, ci, vp, csz, vp, vp, vp,
+                             vp]),
     "mh_strand_volume_accumulate": (ci, [vp, vp, vp, ci, ci, vp, vp, ctypes.c_double, vp, ci, vp, vp, vp, vp]),
     "mh_strand_volume_resolve": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mh_volume_index": (ci, [vp, vp, ci, vp, vp, vp, vp]),

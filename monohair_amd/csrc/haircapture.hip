@@ -12,7 +12,8 @@
 //   mh_capture_resolve_kernel   one lane per pixel: depth, orientation code, confidence code, mask code
 //
 // The photograph rule ("Hair photograph" in the same header, restated by tests/hair_photo_np.py) draws the same strands as
-// 8-bit gray images on an S x S supersampled grid, with the vertex step, the strand lookup and the segment walk above it:
+// 8-bit gray images on an S x S supersampled grid, with the vertex step above it and the strand lookup and the segment walk of
+// mh_hairwalk.h (shared with csrc/hairreproj.hip):
 //   mh_photo_shade_kernel       one lane per segment: the Kajiya-Kay diffuse shade q of the world segment, 0..255
 //   mh_photo_fill_kernel        the key plane set to all ones
 //   mh_photo_front_kernel       one lane per segment: atomicMin of (bits(zf) << 32 | q) on every sub-pixel of its fragments
@@ -25,17 +26,7 @@
 #include <stdint.h>
 
 #include "mh_device.h"
-
-// the strand of point i: the s with offs[s] <= i < offs[s+1] (offs non-decreasing, offs[0] = 0, i < offs[S])
-__device__ __forceinline__ int mh_cap_strand_of(const int64_t *__restrict__ offs, int S, int64_t i) {
-    int lo = 0, hi = S;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > i) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
+#include "mh_hairwalk.h"      // the strand lookup and the segment walk
 
 __global__ __launch_bounds__(256) void mh_capture_project_kernel(MhCapCam cam, const float *__restrict__ pts, int n, float Hf,
                                                                  float Wf, float *__restrict__ vert,
@@ -50,65 +41,6 @@ __global__ __launch_bounds__(256) void mh_capture_project_kernel(MhCapCam cam, c
     vert[3 * (size_t)i + 2] = (-z / 2.0f) * 255.0f;
     // (NaN fails every comparison: an invalid vertex)
     valid[i] = (z < -0.1f && __builtin_fabsf(row) < 1048576.0f && __builtin_fabsf(col) < 1048576.0f) ? 1 : 0;
-}
-
-// What the passes need of segment (i, i+1), the same arithmetic in all of them.
-struct MhCapSeg {
-    double r0, c0, z0, dr, dc, dz;
-    int n;
-    long long qc, qs;
-};
-
-// true: points i and i+1 are consecutive points of one strand and both valid
-__device__ __forceinline__ bool mh_cap_pair(const uint8_t *__restrict__ valid, const int64_t *__restrict__ offs, int S,
-                                            int64_t i) {
-    const int s = mh_cap_strand_of(offs, S, i);
-    return s < S && i + 1 < offs[s + 1] && valid[i] && valid[i + 1];                    // (s = S: i beyond the offsets)
-}
-
-// the walk from (r0, c0, z0) to (r1, c1, z1), in whatever units the caller's grid has: the steps and the sample count.
-// false: the segment is dropped (n > MH_CAP_MAXN)
-__device__ __forceinline__ bool mh_cap_walk(MhCapSeg &sg, double r0, double c0, double z0, double r1, double c1, double z1) {
-    sg.r0 = r0, sg.c0 = c0, sg.z0 = z0;
-    sg.dr = r1 - r0;
-    sg.dc = c1 - c0;
-    sg.dz = z1 - z0;
-    const double m = fmax(fabs(sg.dr), fabs(sg.dc));      // < 2^24: both ends are valid
-    const double nn = fmax(1.0, ceil(m));
-    if (nn > (double)MH_CAP_MAXN) return false;
-    sg.n = (int)nn;
-    return true;
-}
-
-// false: no segment starts at point i (last point of its strand, an invalid end), or it is dropped (n > MH_CAP_MAXN: *too_long)
-__device__ __forceinline__ bool mh_cap_segment(const float *__restrict__ vert, const uint8_t *__restrict__ valid,
-                                               const int64_t *__restrict__ offs, int S, int64_t i, MhCapSeg &sg,
-                                               bool &too_long) {
-    too_long = false;
-    if (!mh_cap_pair(valid, offs, S, i)) return false;
-    if (!mh_cap_walk(sg, (double)vert[3 * i], (double)vert[3 * i + 1], (double)vert[3 * i + 2], (double)vert[3 * i + 3],
-                     (double)vert[3 * i + 4], (double)vert[3 * i + 5])) {
-        too_long = true;
-        return false;
-    }
-    const double len = sqrt(sg.dr * sg.dr + sg.dc * sg.dc);
-    sg.qc = sg.qs = 0;
-    if (len > 0.0) {
-        const double ur = sg.dr / len, uc = sg.dc / len;
-        const double c2 = uc * uc - ur * ur, s2 = -2.0 * (uc * ur);
-        sg.qc = (long long)rint(4096.0 * c2);
-        sg.qs = (long long)rint(4096.0 * s2);
-    }
-    return true;
-}
-
-// sample j of a segment: centre pixel and depth; false when the depth is not finite (no fragment)
-__device__ __forceinline__ bool mh_cap_sample(const MhCapSeg &sg, int j, int &cr, int &cc, float &zf) {
-    const double t = ((double)j + 0.5) / (double)sg.n;
-    cr = (int)rint(sg.r0 + t * sg.dr);
-    cc = (int)rint(sg.c0 + t * sg.dc);
-    zf = (float)(sg.z0 + t * sg.dz);
-    return zf < __builtin_inff();
 }
 
 __global__ __launch_bounds__(256) void mh_capture_fill_kernel(uint32_t *__restrict__ p, uint32_t value, size_t n) {

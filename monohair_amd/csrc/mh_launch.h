@@ -55,6 +55,12 @@ struct MhCapCam {                     // one camera record, by value (a kernel a
 struct MhCapTable {                   // float32 (cos 2 theta_k, sin 2 theta_k) of the 180 orientation codes, by value
     float t[180][2];
 };
+#define MH_SUP_COLS 4                 // capture agreement: visible, on hair, confident, dropped segments; then one per bound
+#define MH_SUP_MAX_BOUNDS 8
+struct MhSupBounds {                  // the agreement bounds 4096 cos(2 angle_k) of the host, by value
+    double b[MH_SUP_MAX_BOUNDS];
+    int n;
+};
 
 #define MH_VOL_MAXN 8192              // strand volume: a segment of more samples than this is dropped and counted
 #define MH_VOL_MAXCNT (1ll << 29)     // ... and a voxel of more samples than this is refused: |q| <= 4096, so every sum stays
@@ -330,6 +336,14 @@ int mh_launch_photo_front(const float *vert, const uint8_t *valid, const int64_t
                           unsigned long long *keys, int32_t *dropped, hipStream_t st);
 int mh_launch_photo_resolve(const unsigned long long *keys, const float *depth0, int H, int W, int ss, int bust_code,
                             int background_code, uint8_t *gray, int32_t *cover, hipStream_t st);
+
+// ---- hairreproj.hip (loads with its first launch)
+int mh_launch_support_accum(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points, int H, int W,
+                            float tol, const float *depth0, const float *zmin, const uint8_t *ori, const uint8_t *conf,
+                            const uint8_t *mask, int conf_min, MhCapTable tab, MhSupBounds bd,
+                            unsigned long long *strand_counts, unsigned long long *view_counts, hipStream_t st);
+int mh_launch_support_silhouette(const float *zmin, const uint8_t *mask, int H, int W, unsigned long long *out3,
+                                 hipStream_t st);
 
 // ---- hairvolume.hip (loads with its first launch)
 int mh_launch_strand_volume_accum(const float *pts, const int64_t *offs, int S, int n_points, MhVolGrid gr, int sub,
