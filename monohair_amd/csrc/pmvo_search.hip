@@ -347,6 +347,7 @@ __device__ __forceinline__ void mh_tap_update(float (&ML)[KA], float (&BC)[KA], 
 #define MH_KEY_MIN_TAPS 10           // lists up to this length go through the select body directly
 #endif
 #define MH_KEY_PAD 4                 // the key block takes this many taps; (0, 0) records fill a last block: cs = 0, t' = C
+#define MH_KEY_WALK_TAPS 49          // lists of this length (a complete 7 x 7 patch) take mh_key_walk instead of the loop over blocks
 // How many taps of a list of c > MH_KEY_MIN_TAPS taps the key blocks walk, and how many tap records the list takes in LDS.
 // Padded to whole blocks, a complete 7 x 7 patch (49 taps: 85 % of the bench scene's lists) ran a thirteenth block for one
 // tap.  The LAST tap of a list does not need a block: its key is the initial value of the accumulator of its parity (a key
@@ -416,6 +417,18 @@ __device__ __forceinline__ unsigned mh_min3u(unsigned a, unsigned b, unsigned c)
 // into ko; the first NI entries of the caller's arrays are used.  (Padding lists to two taps instead of four, with a
 // two-tap block for the tail, was measured: the choice between two asm blocks that update the same registers costs eight
 // register copies and a wait for every LDS read per call -- 0.634 instead of 0.582 ms.)
+// A list of exactly MH_KEY_WALK_TAPS taps (a complete 7 x 7 patch: 85 % of the bench scene's lists) does not loop over its blocks:
+// mh_key_walk<12> is the twelve mh_key_blockm4 statements in a row, FOLD = false and FOLD = true in turn, the block's number and
+// the offsets of its taps constants.  In the loop the waiting keys kk are copied between the registers of the two variants (KA
+// copies per iteration and KA on the back edge), a v_mov_b32 v, s per group rebuilds the LDS address, and a counter, a compare and
+// a branch sit around every block; in straight-line code kk stays where the FOLD = false statement wrote it, ONE base register
+// serves every read through immediate offsets, and nothing is read past the list: 813 / 610 / 407 / 204 instead of 870 / 656 /
+// 442 / 228 VALU instructions per (wave, view) visit for KA = 4 / 3 / 2 / 1, a third of the scalar instructions of the launch
+// gone.  The reads stay C++ statements between the asm statements (their "memory" clobbers keep them in place; the compiler
+// waits with lgkmcnt(2)): an asm operand is a whole register, and v_mul_f32 needs the halves of the pair a 64-bit read writes.
+// Each path makes its own first reads and seed (the walk's at constant offsets): shared in front of the branch they cost the
+// headline kernel six registers and a spill.  The kernels for more than 256 views keep the loop (the walk spills one value
+// there).  profiles/search_walk.txt; tests/test_key_walk_gpu.py.
 #include "mh_key_blocks.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -788,28 +801,37 @@ __device__ __forceinline__ void mh_search_slices_lds(const MhViews &vw, const fl
                     // (tx, ty) of tap i is the first half of record 1 + i
                     const float2 *__restrict__ t2 = reinterpret_cast<const float2 *>(rec + 1);
                     float2 ga[GRP], gb[GRP];
+                    // block 0's taps; the list's last tap seeds the accumulator, under its own block's number
+                    auto first = [&](int is) {
 #pragma unroll
-                    for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * u];
-                    // the list's last tap seeds the accumulator, under its own block's number
-                    const int is = ntap - 1;
-                    const float2 ts = t2[2 * is];
+                        for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * u];
+                        const float2 ts = t2[2 * is];
 #pragma unroll
-                    for (int j = 0; j < KM; ++j)
-                        acc[j] = mh_seed_key(mh_vadd(mh_vmul(ts.x, DX[j]), mh_vmul(ts.y, DY[j])), is >> 2);
-                    for (int t = 0; t < ntp;) {
+                        for (int j = 0; j < KM; ++j)
+                            acc[j] = mh_seed_key(mh_vadd(mh_vmul(ts.x, DX[j]), mh_vmul(ts.y, DY[j])), is >> 2);
+                    };
+                    // uniform: a complete 7 x 7 patch walks its twelve blocks as straight-line code (mh_key_walk; the kernels for
+                    // more than 256 views spill with it and keep the loop)
+                    if (!BIGV && ntap == MH_KEY_WALK_TAPS) {
+                        first(MH_KEY_WALK_TAPS - 1);
+                        if constexpr (KM > 0) mh_key_walk<(MH_KEY_WALK_TAPS - 1) / MH_KEY_PAD, KM, KN>(acc, ga, t2, DX, DY);
+                    } else {
+                        first(ntap - 1);
+                        for (int t = 0; t < ntp;) {
 #pragma unroll
-                        for (int u = 0; u < GRP; ++u) gb[u] = t2[2 * (t + GRP + u)];
-                        if constexpr (KM > 0) mh_key_blockm4<KM, KN, false>(acc, kk, ga, DX, DY, t >> 2);
-                        t += GRP;
-                        if (t >= ntp) {   // an odd number of blocks: the last one folds alone
+                            for (int u = 0; u < GRP; ++u) gb[u] = t2[2 * (t + GRP + u)];
+                            if constexpr (KM > 0) mh_key_blockm4<KM, KN, false>(acc, kk, ga, DX, DY, t >> 2);
+                            t += GRP;
+                            if (t >= ntp) {   // an odd number of blocks: the last one folds alone
 #pragma unroll
-                            for (int j = 0; j < KM; ++j) acc[j] = min(acc[j], kk[j]);
-                            break;
+                                for (int j = 0; j < KM; ++j) acc[j] = min(acc[j], kk[j]);
+                                break;
+                            }
+#pragma unroll
+                            for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * (t + GRP + u)];
+                            if constexpr (KM > 0) mh_key_blockm4<KM, KN, true>(acc, kk, gb, DX, DY, t >> 2);
+                            t += GRP;
                         }
-#pragma unroll
-                        for (int u = 0; u < GRP; ++u) ga[u] = t2[2 * (t + GRP + u)];
-                        if constexpr (KM > 0) mh_key_blockm4<KM, KN, true>(acc, kk, gb, DX, DY, t >> 2);
-                        t += GRP;
                     }
                 }
                 // decode: one compare for "any key past the valid range"; m = the key's upper bits with the constant 0b0011

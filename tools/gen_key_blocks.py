@@ -2,7 +2,9 @@
 """Writes monohair_amd/csrc/mh_key_blocks.h: four taps x NI items of the search kernel's key bodies
 (monohair_amd/csrc/pmvo_search.hip, which includes the header) as one hand-ordered inline-asm block per NI = 4, 3, 2, 1:
 mh_key_block4<NI, KN>, which keys every tap (lists of more than one 64-tap group), and mh_key_blockm4<NI, KN, FOLD>, which
-keys the block (one-group lists).
+keys the block (one-group lists), and mh_key_walk<NB, KM, KN>, the walk of a list of known length (NB blocks in front of its seeded
+last tap) as straight-line code: the statements of mh_key_blockm4, FOLD = false and FOLD = true in turn, each under its block's
+number, the taps of the next block requested in front of it at constant offsets (see walk()).
 
 Order inside a half (two taps of the same parity, items j = 0..NI-1): the instructions of one kind for all items, then the
 next kind, so that every result is used NI - 1 or more instructions after it is produced; the second tap's products are
@@ -156,9 +158,45 @@ __device__ __forceinline__ void mh_key_block4(unsigned (&ke)[KN], unsigned (&ko)
 """
 
 
+WALKS = (12,)   # blocks of the lists that get a walk: 49 taps (7 x 7), the last tap seeded
+
+
+def walk(nb):
+    """The statements of the walk of nb blocks: block i from ga (i even, FOLD = false) or gb (i odd, FOLD = true), the taps of
+    block i + 1 requested in front of it from t2 at constant offsets; an odd last block folds alone."""
+    out = []
+    for i in range(nb):
+        cur, nxt = ("ga", "gb") if i % 2 == 0 else ("gb", "ga")
+        if i + 1 < nb:
+            out.append(" ".join(f"{nxt}[{u}] = t2[{2 * (4 * (i + 1) + u)}];" for u in range(4)))
+        out.append(f"mh_key_blockm4<KM, KN, {'true' if i % 2 else 'false'}>(acc, kk, {cur}, DX, DY, {i});")
+    if nb % 2:
+        out.append("for (int j = 0; j < KM; ++j) acc[j] = min(acc[j], kk[j]);")
+    return out
+
+
+HEADW = """
+// the walk of a list of known length: the NB blocks in front of its seeded last tap as straight-line code -- the parity of a
+// block, its number and the offsets of its taps from t2 (tap 0's (tx, ty); a tap record is two float2) are constants, kk is
+// named only here.  ga holds block 0's taps on entry.
+template <int NB, int KM, int KN>
+__device__ __forceinline__ void mh_key_walk(unsigned (&acc)[KN], float2 (&ga)[4], const float2 *__restrict__ t2,
+                                            const float (&DX)[KN], const float (&DY)[KN]) {
+    static_assert(%s, "mh_key_walk: a generated length");
+    unsigned kk[KN];
+    [[maybe_unused]] float2 gb[4];
+"""
+
+
+def emitw(nb, first):
+    body = "".join(f"        {l}\n" for l in walk(nb))
+    return f"    {'if' if first else 'else if'} constexpr (NB == {nb}) {{\n{body}    }}\n"
+
+
 def header(width=WIDTH, form=FORM):
     return (HEAD + "".join(emit(n) for n in (4, 3, 2, 1)) + "}\n" +
-            HEADM % (width, width) + "".join(emitm_n(n, width, form) for n in (4, 3, 2, 1)) + "}\n")
+            HEADM % (width, width) + "".join(emitm_n(n, width, form) for n in (4, 3, 2, 1)) + "}\n" +
+            HEADW % " || ".join(f"NB == {nb}" for nb in WALKS) + "".join(emitw(nb, i == 0) for i, nb in enumerate(WALKS)) + "}\n")
 
 
 if __name__ == "__main__":
@@ -173,5 +211,5 @@ if __name__ == "__main__":
     args = ap.parse_args()
     text = header(args.width, args.form)
     if args.only_blockm4:
-        text = text[text.index(HEADM[:40]):]
+        text = text[text.index(HEADM[:40]):text.index(HEADW[:40])]
     print(text.replace("mh_key_blockm4", args.name), end="")

@@ -8,9 +8,11 @@
 //      and takes the first that equals m
 //   X  the same with the MAXIMUM first: m = C - max of the block's four |cs| (mh_key_blockm4 as committed: v_max_f32, v_max3_f32
 //      with |.| on the sources, one subtraction); the rest is M's
+//   W  X with the twelve blocks as straight-line code (mh_key_walk<12>: the block numbers, the parities and the offsets of the taps
+//      are constants, no loop, no key copied between the two variants of the block); seed and decode are X's
 // The taps are unit vectors at the angles pi * t / 49, the items' directions are spread over the half circle lane by lane, so that the
 // winning blocks differ among the lanes of a wave (the per-lane LDS reads of M go to twelve or more different blocks; printed).  Both
-// forms add loss * confidence and confidence over the visits; the sums are compared bit for bit (T with M, M with X).
+// forms add loss * confidence and confidence over the visits; the sums are compared bit for bit (T with M, M with X, X with W).
 // 5 waves per SIMD (1280 workgroups of 256 lanes).  ALONE: every wave visits, back to back.  ALTERNATING: every wave projects its four
 // items (the plain chains of tools/ubench/proj_forms.hip, form S) and then visits, the workgroups starting 0, 2, 4, 7 and 9 blocks into
 // that cycle, so that a wave in its decode runs beside waves in their key blocks and in their projection.
@@ -149,8 +151,9 @@ DEV void visit_T(const float4 *rec, int nblk, const float (&DX)[4], const float 
     }
 }
 
-// ---- one visit, form M (MAXF = false) or X (MAXF = true); blk[j] = the winning block of item j
-template <bool MAXF>
+// ---- one visit, form M (MAXF = false), X (MAXF = true) or W (MAXF and WALK; the walk is the whole list's, so the short first
+// visit that staggers the workgroups keeps the loop); blk[j] = the winning block of item j
+template <bool MAXF, bool WALK = false>
 DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float (&DY)[4], float (&ML)[4], float (&BC)[4], unsigned (&blk)[4]) {
     const int ntp = 4 * nblk;
     unsigned acc[4], kk[4];
@@ -163,6 +166,8 @@ DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float 
     const float2 ts = t2[2 * is];
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = keyof(tprime(vadd(vmul(ts.x, DX[j]), vmul(ts.y, DY[j]))), 0, is >> 2);
+    if (WALK && nblk == 12) mh_key_walk<12, 4, 4>(acc, ga, t2, DX, DY);
+    else
     for (int t = 0; t < ntp;) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) gb[u] = t2[2 * (t + 4 + u)];
@@ -208,7 +213,7 @@ DEV void visit_M(const float4 *rec, int nblk, const float (&DX)[4], const float 
     }
 }
 
-// FORM 0 T, 1 M, 2 X.  PROJ: every visit is preceded by the projection of the wave's four items.
+// FORM 0 T, 1 M, 2 X, 3 W.  PROJ: every visit is preceded by the projection of the wave's four items.
 template <int FORM, bool PROJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 visit_kernel(const float *__restrict__ cams, const float4 *__restrict__ list /* [1 + NTAP + 7] */, int visits,
@@ -246,7 +251,7 @@ visit_kernel(const float *__restrict__ cams, const float4 *__restrict__ list /* 
         float ML[4], BC[4];
         const int nblk = (ahead && i == 0) ? ahead : 12;   // (the first, short walk only staggers the workgroups)
         if constexpr (FORM == 0) visit_T(s_taps, nblk, DX, DY, ML, BC);
-        else visit_M<FORM == 2>(s_taps, nblk, DX, DY, ML, BC, blk);
+        else visit_M<FORM >= 2, FORM == 3>(s_taps, nblk, DX, DY, ML, BC, blk);
         if (!(ahead && i == 0)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -340,39 +345,41 @@ int main() {
     const int visits = 2000;
     printf("wall clock %d kHz; %d workgroups x 256 lanes, 5 waves per SIMD; %d visits of 4 items x (seed + 12 blocks + decode) per wave; %d launches each\n",
            rate_khz, WGS, visits, REPS);
-    double med[2][3], spr[2][3];
-    std::vector<float> sums[2][3];
-    std::vector<unsigned> blocks[2][3];
+    double med[2][4], spr[2][4];
+    std::vector<float> sums[2][4];
+    std::vector<unsigned> blocks[2][4];
     if (run<0, false>(d, visits, tick_ns, med[0][0], spr[0][0], sums[0][0], blocks[0][0])) return 1;
     if (run<1, false>(d, visits, tick_ns, med[0][1], spr[0][1], sums[0][1], blocks[0][1])) return 1;
     if (run<2, false>(d, visits, tick_ns, med[0][2], spr[0][2], sums[0][2], blocks[0][2])) return 1;
+    if (run<3, false>(d, visits, tick_ns, med[0][3], spr[0][3], sums[0][3], blocks[0][3])) return 1;
     if (run<0, true>(d, visits, tick_ns, med[1][0], spr[1][0], sums[1][0], blocks[1][0])) return 1;
     if (run<1, true>(d, visits, tick_ns, med[1][1], spr[1][1], sums[1][1], blocks[1][1])) return 1;
     if (run<2, true>(d, visits, tick_ns, med[1][2], spr[1][2], sums[1][2], blocks[1][2])) return 1;
-    const char *mode[2] = {"ALONE      ", "ALTERNATING"}, *form[3] = {"T per-tap keys  ", "M per-block keys", "X maximum first "};
-    const char *nm = "TMX";
+    if (run<3, true>(d, visits, tick_ns, med[1][3], spr[1][3], sums[1][3], blocks[1][3])) return 1;
+    const char *mode[2] = {"ALONE      ", "ALTERNATING"}, *form[4] = {"T per-tap keys  ", "M per-block keys", "X maximum first ", "W straight walk "};
+    const char *nm = "TMXW";
     for (int p = 0; p < 2; ++p)
-        for (int f = 0; f < 3; ++f)
+        for (int f = 0; f < 4; ++f)
             printf("%s %s per (wave, view) visit%s: SIMD %7.2f ns = %6.1f cycles@2.4GHz, spread %.2f ns\n", mode[p], form[f],
                    p ? " with its projection" : "", med[p][f], med[p][f] * 2.4, spr[p][f]);
     for (int p = 0; p < 2; ++p)
-        for (int f = 1; f < 3; ++f) {   // M against T, X against M
+        for (int f = 1; f < 4; ++f) {   // M against T, X against M, W against X
             const double gain = med[p][f - 1] - med[p][f], noise = std::max(spr[p][f - 1], spr[p][f]);
             printf("%s %c is %+.2f ns = %+.1f cycles (%+.1f %%) against %c; larger spread %.2f ns: %s\n", mode[p], nm[f], -gain, -gain * 2.4,
                    -100.0 * gain / med[p][f - 1], nm[f - 1], noise, gain > noise ? "cheaper by more than the spread" : "NOT cheaper by more than the spread");
         }
     bool same = true;
     for (int p = 0; p < 2; ++p)
-        for (int f = 1; f < 3; ++f) same = same && memcmp(sums[p][0].data(), sums[p][f].data(), sizeof(float) * sums[p][0].size()) == 0;
+        for (int f = 1; f < 4; ++f) same = same && memcmp(sums[p][0].data(), sums[p][f].data(), sizeof(float) * sums[p][0].size()) == 0;
     bool same_blocks = true;
-    for (int p = 0; p < 2; ++p) same_blocks = same_blocks && blocks[p][1] == blocks[p][2];
+    for (int p = 0; p < 2; ++p) same_blocks = same_blocks && blocks[p][1] == blocks[p][2] && blocks[p][2] == blocks[p][3];
     int distinct = 0;
     {
         bool seen[16] = {};
         for (int l = 0; l < 64; ++l) seen[blocks[0][1][l * 4] & 15u] = true;   // item 0 of the lanes of wave 0
         for (int i = 0; i < 16; ++i) distinct += seen[i] ? 1 : 0;
     }
-    printf("sums of loss * confidence and of confidence, 1024 items of workgroup 0: T, M and X %s; winning blocks of M and X %s; winning blocks of item 0 among the 64 lanes of wave 0: %d different\n",
+    printf("sums of loss * confidence and of confidence, 1024 items of workgroup 0: T, M, X and W %s; winning blocks of M, X and W %s; winning blocks of item 0 among the 64 lanes of wave 0: %d different\n",
            same ? "bit-equal" : "DIFFER", same_blocks ? "equal" : "DIFFER", distinct);
     return same && same_blocks ? 0 : 2;
 }
