@@ -369,7 +369,10 @@ int mh_gabor_view(mh_ctx *ctx, const uint8_t *gray, int H, int W, const double *
  *   {ori_x, -ori_y, -ori_z, occ} (HairGrowing.__init__, HairGrow.py:41-55); vox: W*H*Z*16 bytes.
  * mh_trace_seeds: HairGrowing.trace (:59-149) for n already-jittered seeds, WITHOUT the flag gate: strand i occupies
  *   out[i][first[i] .. first[i]+len[i]) of a 513-point row.
- * mh_trace_scalp: HairGrowing.traceFromScalp (:154-223): rows of 257 points, len 0 where the reference returns None.
+ * mh_trace_scalp: HairGrowing.traceFromScalp (:154-223): rows of 257 points, len 0 where the reference returns None.  Such
+ *   a rejected walk -- one still inside the head after 25 steps -- leaves the points it took in its own row, the seed and
+ *   exactly 25 steps in slots 0 .. 25 (no caller reads a row past its len, and every caller allocates whole rows); nothing
+ *   else of the row, and no other row, is written.
  * mh_strands_accept: the sequential flag gate of GenerateGuideStrandFromScalp (:226-265) / randomlyGenerateSegments
  *   (:269-299) replayed over the finished traces -- HOST pointers, runs on the calling thread. */
 int mh_volume_pack(mh_ctx *ctx, const float *occ, const float *ori, int W, int H, int Z, void *vox, void *stream);

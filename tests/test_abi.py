@@ -27,15 +27,22 @@ def declared_prototypes(headers=("mh_pmvo.h", "mh_pmvo_lab.h")):
             words = words[:-1]       # the parameter's name
         return " ".join(words)
 
+    return {name: (kind(ret, False), [kind(q, True) for q in params])
+            for name, (ret, params) in declared_parameters(headers).items()}
+
+
+def declared_parameters(headers=("mh_pmvo.h", "mh_pmvo_lab.h")):
+    """{name: (return declaration, [parameter declarations])} of every prototype, as written (comments removed, blanks
+    folded): what tells a `const float *` from a `float *`"""
     out = {}
     for h in headers:
         hdr = open(os.path.join(ROOT, "include", h)).read()
         hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
         hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
         for ret, name, params in re.findall(r"([^;{}()]*?)\b(mh_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr):
-            params = [] if params.strip() in ("", "void") else [kind(q, True) for q in params.split(",")]
+            params = [] if params.strip() in ("", "void") else [" ".join(q.split()) for q in params.split(",")]
             assert name not in out, name
-            out[name] = (kind(ret, False), params)
+            out[name] = (" ".join(ret.split()), params)
     return out
 
 
