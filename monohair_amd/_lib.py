@@ -176,12 +176,33 @@ def check(rc, what=""):
         raise MhError("%s failed (%d): %s" % (what or "libmhpmvo", rc, msg.decode() if msg else "?"))
 
 
-def ptr(t):
-    """data pointer of a torch tensor (or None)."""
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+def ptr(t, row=0, width=1):
+    """data pointer of a torch tensor (or None); of row `row` of a contiguous one with `width` elements per row."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr() + row * width * t.element_size())
 
 
-def stream_ptr():
+def host_ptr(a):
+    """data pointer of a contiguous numpy array."""
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def stream_ptr(stream=None):
+    """handle of a torch stream; of the current one by default."""
     import torch
 
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return ctypes.c_void_p((torch.cuda.current_stream() if stream is None else stream).cuda_stream)
+
+
+def bare_ctx(device):
+    """A bare library context for kernels that need no views (medoid, Gabor), one per device, kept."""
+    key = str(device)
+    if key not in _bare_ctx:
+        import torch
+
+        h = ctypes.c_void_p()
+        check(lib().mh_ctx_create(torch.device(device).index or 0, ctypes.byref(h)), "mh_ctx_create")
+        _bare_ctx[key] = h
+    return _bare_ctx[key]
+
+
+_bare_ctx = {}

@@ -109,7 +109,7 @@ def all_gather_views(local, n_views, shape, dtype, device):
 
 def refine_sharded():
     """Does `refine` shard its per-point stages over the ranks?  Default since round 6: NO -- every rank runs the
-    device-resident pass on all points (pmvo.py::_refine_device: ~10 ms at the headline size, no communication at all) and
+    device-resident pass on all points (refine.py::_refine_device: ~10 ms at the headline size, no communication at all) and
     rank 0 writes the files.  The sharded smoothing loop pays two small all_gathers per 5000-point chunk -- 116 collectives of
     >= 20 us each at 58 chunks, i.e. at least what the WHOLE single-rank loop takes (3.6 ms) -- and hands its shell stage and
     voxel fit to the host-driven path.  MH_REFINE_SHARD=1 selects it (kept, and pinned to the reference's four-chunk run with 2
@@ -220,14 +220,13 @@ def rccl_comm(device):
     import ctypes
 
     from . import _lib
-    from .pmvo_utils import _ctx_for
 
     d = _dist()
     dev = torch.device(device)
     key = (dev.index or 0, world(), rank())
     if key not in _COMMS:
         L = _lib.lib()
-        ctx = _ctx_for(dev)
+        ctx = _lib.bare_ctx(dev)
         raw = (ctypes.c_ubyte * 128)()
         id_error = None
         if rank() == 0:
@@ -288,8 +287,6 @@ def volume_reduce(vol, device, mode=0, root=0):
     """mh_volume_reduce on a dense [X,Y,Z,C] fp32 device tensor whose x-slabs were filled by their owners: after the
     call (stream-ordered on the current stream) rank `root` holds the whole volume.  mode 0: slab gather
     (ncclSend/ncclRecv, direct to the root); mode 1: dense ncclReduce(sum)."""
-    import ctypes
-
     from . import _lib
 
     assert vol.is_cuda and vol.dtype == torch.float32 and vol.is_contiguous() and vol.dim() == 4
@@ -298,16 +295,13 @@ def volume_reduce(vol, device, mode=0, root=0):
     slabs = slab_bounds(X, world())
     with torch.cuda.device(vol.device):
         _lib.check(_lib.lib().mh_volume_reduce(ctx, comm, rank(), world(), root, _lib.ptr(vol), X, Y, Z, C,
-                                               slabs.ctypes.data_as(ctypes.c_void_p), int(mode), _lib.stream_ptr()),
-                   "mh_volume_reduce")
+                                               _lib.host_ptr(slabs), int(mode), _lib.stream_ptr()), "mh_volume_reduce")
     return vol
 
 
 def volume_gather(slab, vol, grid, device, root=0, handles=None):
     """mh_volume_gather: `slab` = this rank's own [b[r+1]-b[r], Y, Z, C] fp32 device tensor (on the root it may be the
     view vol[b[r]:b[r+1]] itself: no copy), `vol` = the dense [X,Y,Z,C] tensor on the root, None elsewhere."""
-    import ctypes
-
     from . import _lib
 
     X, Y, Z, C = (int(v) for v in grid)
@@ -322,8 +316,7 @@ def volume_gather(slab, vol, grid, device, root=0, handles=None):
     with torch.cuda.device(torch.device(device)):
         _lib.check(_lib.lib().mh_volume_gather(ctx, comm, r, world(), root, _lib.ptr(slab) if slab is not None and
                                                slab.numel() else None, _lib.ptr(vol), X, Y, Z, C,
-                                               slabs.ctypes.data_as(ctypes.c_void_p), _lib.stream_ptr()),
-                   "mh_volume_gather")
+                                               _lib.host_ptr(slabs), _lib.stream_ptr()), "mh_volume_gather")
     return vol
 
 

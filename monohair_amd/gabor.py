@@ -6,7 +6,6 @@ The 180 kernels are built on the host with the same CPU torch ops as gabor_fn (s
 bits) and installed once with mh_gabor_set_bank; the 1.49 GB response stack of the reference never exists.
 File IO uses PIL; the difference-of-Gaussians prefilter is scikit-image's documented definition evaluated with
 scipy.ndimage (third-party arithmetic, unpinned -- SURVEY.md §8c)."""
-import ctypes
 import math
 import os
 
@@ -14,7 +13,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pmvo_utils import _ctx_for
 
 NUM_KERNELS = 180
 KSIZE = 17
@@ -62,10 +60,10 @@ class calOrientationGabor:
         if not torch.cuda.is_available():
             raise _lib.MhError("calOrientationGabor needs a ROCm GPU (no CPU fallback)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self._ctx = _ctx_for(self.device)
+        self._ctx = _lib.bare_ctx(self.device)
         bank = gabor_bank() if bank is None else np.asarray(bank)
         bank = np.ascontiguousarray(bank.reshape(NUM_KERNELS, KSIZE * KSIZE), dtype=np.float32)
-        _lib.check(_lib.lib().mh_gabor_set_bank(self._ctx, bank.ctypes.data_as(ctypes.c_void_p)), "mh_gabor_set_bank")
+        _lib.check(_lib.lib().mh_gabor_set_bank(self._ctx, _lib.host_ptr(bank)), "mh_gabor_set_bank")
         self.set_variant(variant)
         th = orientation_table()
         self._theta = th.to(self.device)
@@ -119,8 +117,8 @@ class calOrientationGabor:
         c8 = torch.empty((H, W), dtype=torch.uint8, device=self.device) if codes else None
         w0, r0, w1, r1 = _dog_weights(low_sigma, high_sigma)
         with torch.cuda.device(self.device):
-            _lib.check(L.mh_gabor_view(self._ctx, _lib.ptr(g), H, W, w0.ctypes.data_as(ctypes.c_void_p), r0,
-                                       w1.ctypes.data_as(ctypes.c_void_p), r1, _lib.ptr(scratch), _lib.ptr(idx),
+            _lib.check(L.mh_gabor_view(self._ctx, _lib.ptr(g), H, W, _lib.host_ptr(w0), r0,
+                                       _lib.host_ptr(w1), r1, _lib.ptr(scratch), _lib.ptr(idx),
                                        _lib.ptr(conf), _lib.ptr(var), _lib.ptr(k8), _lib.ptr(c8), _lib.stream_ptr()),
                        "mh_gabor_view")
         return idx, conf, var, k8, c8
@@ -137,7 +135,7 @@ class calOrientationGabor:
         if getattr(self, "_bank_key", (1.8, 2.4, 4.0)) != key:
             bank = torch.stack([gabor_fn(KSIZE, math.pi * k / NUM_KERNELS, *key) for k in range(NUM_KERNELS)]).numpy()
             bank = np.ascontiguousarray(bank.reshape(NUM_KERNELS, KSIZE * KSIZE), dtype=np.float32)
-            _lib.check(_lib.lib().mh_gabor_set_bank(self._ctx, bank.ctypes.data_as(ctypes.c_void_p)), "mh_gabor_set_bank")
+            _lib.check(_lib.lib().mh_gabor_set_bank(self._ctx, _lib.host_ptr(bank)), "mh_gabor_set_bank")
             self._bank_key = key
 
     def filter(self, image, label, threshold, variance_data, orient_data, max_resp_data, sigma_x=1.8, sigma_y=2.4,
@@ -292,8 +290,8 @@ def difference_of_gaussians_device(image, low_sigma, high_sigma, device, out32=F
     scratch = torch.empty((L.mh_dog_scratch_bytes(H, W),), dtype=torch.uint8, device=device)
     out = torch.empty((H, W), dtype=torch.float32 if out32 else torch.float64, device=device)
     with torch.cuda.device(device):
-        _lib.check(L.mh_dog(_ctx_for(device), _lib.ptr(x), 0 if x.dtype == torch.uint8 else 1, H, W,
-                            w0.ctypes.data_as(ctypes.c_void_p), r0, w1.ctypes.data_as(ctypes.c_void_p), r1,
+        _lib.check(L.mh_dog(_lib.bare_ctx(device), _lib.ptr(x), 0 if x.dtype == torch.uint8 else 1, H, W,
+                            _lib.host_ptr(w0), r0, _lib.host_ptr(w1), r1,
                             _lib.ptr(scratch), None if out32 else _lib.ptr(out), _lib.ptr(out) if out32 else None,
                             _lib.stream_ptr()), "mh_dog")
     return out

@@ -20,8 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hairvolume import _dims, _hp, _load_side
-from .pmvo_utils import GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE, _ctx_for
+from ._lib import host_ptr
+from .hairvolume import _dims, _load_side
+from .pmvo_utils import GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE
 from .timing import stage
 
 MAX_SWEEPS = 1024
@@ -70,7 +71,7 @@ def _bust_planes(pmvo, bust):
 def _votes_dev(pmvo, bust, vmin, vs, dims):
     nvox = int(np.prod(dims.astype(np.int64)))
     counts = torch.empty((nvox, 4), dtype=torch.int32, device=pmvo.device)
-    _lib.check(_lib.lib().mh_inner_votes(pmvo._ctx, _lib.ptr(bust), _hp(vmin), vs, _hp(dims), _lib.ptr(counts),
+    _lib.check(_lib.lib().mh_inner_votes(pmvo._ctx, _lib.ptr(bust), host_ptr(vmin), vs, host_ptr(dims), _lib.ptr(counts),
                                          _lib.stream_ptr()), "mh_inner_votes")
     return counts
 
@@ -98,14 +99,14 @@ def _domain_dev(pmvo, counts, ext_voxels, dims, max_bad):
         ev = torch.from_numpy(ext).to(device)
         ext_index = torch.empty(nvox, dtype=torch.int32, device=device)
         status = torch.empty(2, dtype=torch.int32, device=device)
-        _lib.check(L.mh_volume_index(pmvo._ctx, _lib.ptr(ev), ext.shape[0], _hp(dims), _lib.ptr(ext_index), _lib.ptr(status), st),
-                   "mh_volume_index")
+        _lib.check(L.mh_volume_index(pmvo._ctx, _lib.ptr(ev), ext.shape[0], host_ptr(dims), _lib.ptr(ext_index),
+                                     _lib.ptr(status), st), "mh_volume_index")
         outside, twice = (int(s) for s in status.cpu().numpy())
         if outside or twice:
             raise ValueError("the exterior voxels must be unique and inside the grid: %d outside, %d listed again"
                              % (outside, twice))
     flags = torch.empty(nvox, dtype=torch.uint8, device=device)
-    _lib.check(L.mh_inner_domain(pmvo._ctx, _lib.ptr(counts), _lib.ptr(ext_index), _hp(dims), max_bad, _lib.ptr(flags), st),
+    _lib.check(L.mh_inner_domain(pmvo._ctx, _lib.ptr(counts), _lib.ptr(ext_index), host_ptr(dims), max_bad, _lib.ptr(flags), st),
                "mh_inner_domain")
     index = torch.empty(nvox, dtype=torch.int32, device=device)
     count = torch.empty(1, dtype=torch.int32, device=device)
@@ -154,7 +155,7 @@ def diffuse_orientation(ext_voxels, ext_ori, domain_voxels, grid_resolution=GRID
     nvox = int(np.prod(dims.astype(np.int64)))
     L = _lib.lib()
     with torch.cuda.device(device):
-        ctx, st = _ctx_for(device), _lib.stream_ptr()
+        ctx, st = _lib.bare_ctx(device), _lib.stream_ptr()
         evd, eod, dvd = (torch.from_numpy(a).to(device) for a in (ev, eo, dv))
         vmap = torch.empty(nvox, dtype=torch.int32, device=device)
         ext_t = torch.empty((G, 6), dtype=torch.float64, device=device)
@@ -165,7 +166,7 @@ def diffuse_orientation(ext_voxels, ext_ori, domain_voxels, grid_resolution=GRID
         depth = torch.empty(D, dtype=torch.int32, device=device)
         status = torch.empty(2, dtype=torch.int32, device=device)
         with stage("hairfill: sweeps", device):
-            _lib.check(L.mh_inner_diffuse(ctx, _lib.ptr(evd), _lib.ptr(eod), G, _lib.ptr(dvd), D, _hp(dims), sweeps,
+            _lib.check(L.mh_inner_diffuse(ctx, _lib.ptr(evd), _lib.ptr(eod), G, _lib.ptr(dvd), D, host_ptr(dims), sweeps,
                                           _lib.ptr(vmap), _lib.ptr(ext_t), _lib.ptr(ext_s), _lib.ptr(cell), _lib.ptr(t_a),
                                           _lib.ptr(t_b), _lib.ptr(k_a), _lib.ptr(k_b), _lib.ptr(depth), _lib.ptr(status), st),
                        "mh_inner_diffuse")
@@ -176,8 +177,9 @@ def diffuse_orientation(ext_voxels, ext_ori, domain_voxels, grid_resolution=GRID
         world, ori = (torch.empty((D, 3), dtype=torch.float32, device=device) for _ in range(2))
         coh = torch.empty(D, dtype=torch.float64, device=device)
         emit = torch.empty(D, dtype=torch.uint8, device=device)
-        _lib.check(L.mh_inner_resolve(ctx, _lib.ptr(dvd), D, _lib.ptr(t_a), _lib.ptr(k_a), _hp(vmin), vs, _hp(dims), min_coh,
-                                      _lib.ptr(world), _lib.ptr(ori), _lib.ptr(coh), _lib.ptr(emit), st), "mh_inner_resolve")
+        _lib.check(L.mh_inner_resolve(ctx, _lib.ptr(dvd), D, _lib.ptr(t_a), _lib.ptr(k_a), host_ptr(vmin), vs, host_ptr(dims),
+                                      min_coh, _lib.ptr(world), _lib.ptr(ori), _lib.ptr(coh), _lib.ptr(emit), st),
+                   "mh_inner_resolve")
         w_out, o_out = (torch.empty((D, 3), dtype=torch.float32, device=device) for _ in range(2))
         count = torch.zeros(1, dtype=torch.int32, device=device)
         if D:

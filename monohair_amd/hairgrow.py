@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pmvo_utils import (VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
+from ._lib import host_ptr
+from .pmvo_utils import (VOXEL_SIZE, get_ground_truth_3D_occ, get_ground_truth_3D_ori, load_strand,
                          points_to_voxel, read_obj_normals, save_hair_strands, save_volume_mat_sparse, voxel_to_points)
 from .strand_smooth import pack_strands, smooth_strands, split_strands, strand_offsets
 
@@ -28,10 +29,6 @@ _KNN_K = 50                                                      # k of the refe
 _VMIN64 = np.array([-0.32, -0.32, -0.24], np.float32).astype(np.float64)   # points_to_voxel's float32 voxel_min
 _TYPES = ("root", "tip")
 _OUTSIDE = "%s indexes outside the occupancy volume (the reference's torch indexing raises IndexError here)"
-
-
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _td(a, dev):
@@ -78,7 +75,7 @@ class HairGrowing:
         occ_t = torch.from_numpy(np.ascontiguousarray(occ[..., 0])).to(self.device).float()          # [Z,H,W]
         ori_t = torch.from_numpy(np.ascontiguousarray(ori)).to(self.device).float()                  # [Z,H,W,3]
         self.Z, self.H, self.W = occ_t.shape
-        self._ctx = _ctx_for(self.device)
+        self._ctx = _lib.bare_ctx(self.device)
         self._vox = torch.empty((self.Z, self.H, self.W, 4), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mh_volume_pack(self._ctx, _lib.ptr(occ_t), _lib.ptr(ori_t), self.W, self.H, self.Z,
@@ -129,8 +126,8 @@ class HairGrowing:
         assert total < 2 ** 31
         offs32 = offs_h.astype(np.int32)
         acc = np.zeros(n, np.uint8)
-        _lib.check(_lib.lib().mh_strands_accept(self.W, self.H, self.Z, _hp(flag), _hp(pts_h), _hp(offs32), _hp(ln_h),
-                                                0, _hp(seeds_h), n, mode, _hp(acc)), "mh_strands_accept")
+        _lib.check(_lib.lib().mh_strands_accept(self.W, self.H, self.Z, host_ptr(flag), host_ptr(pts_h), host_ptr(offs32),
+                                                host_ptr(ln_h), 0, host_ptr(seeds_h), n, mode, host_ptr(acc)), "mh_strands_accept")
         return split_strands(pts_h, offs_h, np.flatnonzero(acc))
 
     def _voxel_rounds(self, flag, thrDot, rounds):
@@ -254,7 +251,7 @@ class HairGrowing:
         int32 [N], 1 accepted, 0 rejected, 2 outside the reference's box, 3 an index torch refuses."""
         Z, H, W = occ_v.shape
         status = torch.empty((N,), dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().mh_occ_check(self._ctx, _lib.ptr(out), _lib.ptr(ooffs), N, ctypes.c_void_p(occ_v.data_ptr()),
+        _lib.check(_lib.lib().mh_occ_check(self._ctx, _lib.ptr(out), _lib.ptr(ooffs), N, _lib.ptr(occ_v),
                                            occ_v.stride(-1), W, H, Z, float(_VMIN64[0]), float(_VMIN64[1]),
                                            float(_VMIN64[2]), VOXEL_SIZE, _lib.ptr(status), _lib.stream_ptr()),
                    "mh_occ_check")
@@ -343,9 +340,9 @@ class HairGrowing:
         c.grid = np.array([c.lo[0], c.lo[1], c.lo[2], h], np.float32)
         c.dims = np.array(dims, np.int32)
         c.cstart = torch.empty(int(np.prod(dims)) + 1, dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().mh_grid_build(self._ctx, _hp(c.grid), _hp(c.dims), _lib.ptr(c.pts), c.M, _lib.ptr(c.scratch),
-                                            c.scratch.numel(), None, _lib.ptr(c.order), _lib.ptr(c.cstart), None,
-                                            _lib.stream_ptr()), "mh_grid_build")
+        _lib.check(_lib.lib().mh_grid_build(self._ctx, host_ptr(c.grid), host_ptr(c.dims), _lib.ptr(c.pts), c.M,
+                                            _lib.ptr(c.scratch), c.scratch.numel(), None, _lib.ptr(c.order), _lib.ptr(c.cstart),
+                                            None, _lib.stream_ptr()), "mh_grid_build")
         c.grid_thr = thr_dist
 
     def _scalp_pass(self, s, c, act, thr_dist, thr_dot, out_ratio):
@@ -356,7 +353,7 @@ class HairGrowing:
         n, nact = s.flags.shape[0], int(act.shape[0])
         bcnt = torch.empty(nact, dtype=torch.int64, device=dev)
         _lib.check(L.mh_scalp_ball_count(ctx, _lib.ptr(s.P), _lib.ptr(s.offs), _lib.ptr(act), nact, _lib.ptr(c.pts), c.M,
-                                         _lib.ptr(c.order), _lib.ptr(c.cstart), _hp(c.grid), _hp(c.dims), thr_dist,
+                                         _lib.ptr(c.order), _lib.ptr(c.cstart), host_ptr(c.grid), host_ptr(c.dims), thr_dist,
                                          _lib.ptr(bcnt), st), "mh_scalp_ball_count")
         boff = torch.zeros(nact + 1, dtype=torch.int64, device=dev)
         torch.cumsum(bcnt, 0, out=boff[1:])
@@ -366,7 +363,7 @@ class HairGrowing:
         bidx = torch.zeros(n, dtype=torch.int32, device=dev)
         _lib.check(L.mh_scalp_choose(ctx, _lib.ptr(s.P), _lib.ptr(s.offs), _lib.ptr(act), nact, _lib.ptr(c.pts),
                                      _lib.ptr(c.sid), _lib.ptr(c.rank), c.M, _lib.ptr(c.order), _lib.ptr(c.cstart),
-                                     _hp(c.grid), _hp(c.dims), thr_dist, thr_dot, _lib.ptr(s.oratio), _lib.ptr(boff),
+                                     host_ptr(c.grid), host_ptr(c.dims), thr_dist, thr_dot, _lib.ptr(s.oratio), _lib.ptr(boff),
                                      _lib.ptr(bscr), _lib.ptr(flip), _lib.ptr(bsid), _lib.ptr(bidx), st), "mh_scalp_choose")
         joined = bsid >= 0
         newlen = (s.offs[1:] - s.offs[:-1]) + torch.where(joined, bidx.long() + 1, torch.zeros_like(bidx).long())
@@ -495,7 +492,7 @@ def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, dev
         raise _lib.MhError("sample_scalp: uniforms must be [n,2] in [0,1)")
     bust = np.ascontiguousarray(np.asarray(bust_to_origin, dtype=np.float64).reshape(3))
     dev, L = torch.device(device), _lib.lib()
-    ctx = _ctx_for(dev)
+    ctx = _lib.bare_ctx(dev)
     v_d, vn_d, f_d = _td(v, dev), _td(vn, dev), _td(f.astype(np.int32), dev)
     area = torch.empty((nf,), dtype=torch.float64, device=dev)
     pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -508,7 +505,7 @@ def sample_scalp(scalp_path, bust_to_origin, number_of_points=60000, seed=0, dev
         B = scalp_allocation(area_h, n)
         B_d, u_d = _td(B, dev), _td(u, dev)
         _lib.check(L.mh_mesh_sample(ctx, _lib.ptr(v_d), _lib.ptr(vn_d), nv, _lib.ptr(f_d), nf, _lib.ptr(B_d), _lib.ptr(u_d),
-                                    n, _hp(bust), _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(tri), _lib.stream_ptr()),
+                                    n, host_ptr(bust), _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(tri), _lib.stream_ptr()),
                    "mh_mesh_sample")
     if return_details:
         return pts, nrm, dict(area=area_h, bounds=B, triangle=tri)
@@ -539,7 +536,7 @@ def diffusion_scalp(points, normals, ori, occ, device="cuda:0", return_details=F
     if not torch.cuda.is_available():
         raise _lib.MhError("diffusion_scalp needs a ROCm GPU (no CPU fallback)")
     dev, L = torch.device(device), _lib.lib()
-    ctx = _ctx_for(dev)
+    ctx = _lib.bare_ctx(dev)
     pts = torch.as_tensor(points).to(dev).type(torch.float).reshape(-1, 3).contiguous()
     nrm = torch.as_tensor(normals).to(dev).type(torch.float).reshape(-1, 3).contiguous()
     ori_o = torch.as_tensor(ori).to(dev).type(torch.float).contiguous().clone()

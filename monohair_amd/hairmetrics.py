@@ -10,7 +10,6 @@ in include/mh_pmvo.h and restated in numpy by tests/hair_metrics_np.py: float64 
 The kernels are csrc/hairmetrics.hip; the targets' grid is mh_grid_build's (csrc/sortgroup.hip) with the cell rule of
 hairgrow.grid_dims.  There is no CPU path."""
 import argparse
-import ctypes
 import json
 import math
 import sys
@@ -19,8 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import host_ptr
 from .hairgrow import grid_dims
-from .pmvo_utils import _ctx_for, load_strand
+from .pmvo_utils import load_strand
 
 DEFAULT_THRESHOLDS = ((0.001, 10.0), (0.002, 20.0), (0.003, 30.0))   # (metres, degrees)
 MAX_PAIRS = 8                                                        # one bit of the flag byte each
@@ -54,10 +54,6 @@ def threshold_bounds(dist, angle_deg):
     return [float(d) * float(d) for d in dist], [math.cos(float(a) * (math.pi / 180.0)) for a in angle_deg]
 
 
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _dev(a, dtype, device):
     if isinstance(a, torch.Tensor):
         return a.to(device=device, dtype=dtype).contiguous()
@@ -85,7 +81,7 @@ def _resample_dev(counts, offs, pts, step, device):
         raise ValueError("step must be a positive length, got %r" % step)
     if pts.shape[0] == 0:
         return counts, offs, pts
-    L, ctx, st = _lib.lib(), _ctx_for(device), _lib.stream_ptr()
+    L, ctx, st = _lib.lib(), _lib.bare_ctx(device), _lib.stream_ptr()
     cum = torch.empty(max(pts.shape[0], 1), dtype=torch.float64, device=device)
     m = torch.empty(S, dtype=torch.int64, device=device)
     _lib.check(L.mh_strand_arclen(ctx, _lib.ptr(pts), _lib.ptr(offs), S, step, _lib.ptr(cum), _lib.ptr(m), st),
@@ -105,7 +101,7 @@ def _tangents_dev(counts, offs, pts, device):
     n = pts.shape[0]
     tan = torch.empty((n, 3), dtype=torch.float64, device=device)
     valid = torch.empty(n, dtype=torch.uint8, device=device)
-    _lib.check(_lib.lib().mh_strand_tangents(_ctx_for(device), _lib.ptr(pts), _lib.ptr(offs), counts.shape[0], n,
+    _lib.check(_lib.lib().mh_strand_tangents(_lib.bare_ctx(device), _lib.ptr(pts), _lib.ptr(offs), counts.shape[0], n,
                                              _lib.ptr(tan), _lib.ptr(valid), _lib.stream_ptr()), "mh_strand_tangents")
     return tan, valid
 
@@ -135,7 +131,7 @@ class _Targets:
         self.n = M = int(pts.shape[0])
         if M == 0:
             return
-        L, ctx, st = _lib.lib(), _ctx_for(device), _lib.stream_ptr()
+        L, ctx, st = _lib.lib(), _lib.bare_ctx(device), _lib.stream_ptr()
         box = torch.empty(6, dtype=torch.float32, device=device)
         _lib.check(L.mh_points_bbox(ctx, _lib.ptr(pts), M, _lib.ptr(box), st), "mh_points_bbox")
         box = box.cpu().numpy()
@@ -151,7 +147,7 @@ class _Targets:
         self.pts = torch.empty((M, 3), dtype=torch.float32, device=device)
         order = torch.empty(M, dtype=torch.int32, device=device)
         self.cstart = torch.empty(int(np.prod(dims)) + 1, dtype=torch.int32, device=device)
-        _lib.check(L.mh_grid_build(ctx, _hp(self.grid), _hp(self.dims), _lib.ptr(pts), M, _lib.ptr(self.scratch),
+        _lib.check(L.mh_grid_build(ctx, host_ptr(self.grid), host_ptr(self.dims), _lib.ptr(pts), M, _lib.ptr(self.scratch),
                                    self.scratch.numel(), _lib.ptr(self.pts), _lib.ptr(order), _lib.ptr(self.cstart), None,
                                    st), "mh_grid_build")
         self.tan = tan[order.long()].contiguous()
@@ -162,16 +158,16 @@ def _match_dev(q_pts, q_tan, q_valid, targets, r2, cos, device):
     out = torch.zeros(nq, dtype=torch.uint8, device=device)
     if nq == 0 or targets.n == 0:
         return out
-    L, ctx, st = _lib.lib(), _ctx_for(device), _lib.stream_ptr()
+    L, ctx, st = _lib.lib(), _lib.bare_ctx(device), _lib.stream_ptr()
     scratch = torch.empty(int(L.mh_grid_scratch_bytes(nq)), dtype=torch.uint8, device=device)
     q_order = torch.empty(nq, dtype=torch.int32, device=device)
-    _lib.check(L.mh_grid_build(ctx, _hp(targets.grid), _hp(targets.dims), _lib.ptr(q_pts), nq, _lib.ptr(scratch),
+    _lib.check(L.mh_grid_build(ctx, host_ptr(targets.grid), host_ptr(targets.dims), _lib.ptr(q_pts), nq, _lib.ptr(scratch),
                                scratch.numel(), None, _lib.ptr(q_order), None, None, st), "mh_grid_build")
     r2h, ch = np.asarray(r2, np.float64), np.asarray(cos, np.float64)
     _lib.check(L.mh_strand_match(ctx, _lib.ptr(q_pts), _lib.ptr(q_tan), _lib.ptr(q_valid), _lib.ptr(q_order), nq,
                                  _lib.ptr(targets.pts), _lib.ptr(targets.tan), targets.n, _lib.ptr(targets.cstart),
-                                 _hp(targets.grid), _hp(targets.dims), _hp(r2h), _hp(ch), int(r2h.shape[0]), _lib.ptr(out),
-                                 st), "mh_strand_match")
+                                 host_ptr(targets.grid), host_ptr(targets.dims), host_ptr(r2h), host_ptr(ch), int(r2h.shape[0]),
+                                 _lib.ptr(out), st), "mh_strand_match")
     return out
 
 
@@ -203,7 +199,7 @@ def match_flags(q_pts, q_tan, q_valid, t_pts, t_tan, t_valid, dist=None, angle_d
 
 def _flag_counts(flags, valid, device):
     out = torch.empty(9, dtype=torch.int64, device=device)
-    _lib.check(_lib.lib().mh_flag_counts(_ctx_for(device), _lib.ptr(flags), _lib.ptr(valid), int(flags.shape[0]),
+    _lib.check(_lib.lib().mh_flag_counts(_lib.bare_ctx(device), _lib.ptr(flags), _lib.ptr(valid), int(flags.shape[0]),
                                          _lib.ptr(out), _lib.stream_ptr()), "mh_flag_counts")
     return [int(v) for v in out.cpu().numpy()]
 

@@ -12,7 +12,6 @@ by tests/hair_reproj_np.py; the kernels are csrc/hairreproj.hip on top of the ca
 (csrc/haircapture.hip).  Every counter is an integer sum, so a run leaves the same numbers whatever order the GPU worked in.
 There is no CPU path."""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -22,8 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import host_ptr
 from .camera import camera_records
-from .pmvo_utils import _ctx_for, load_strand, map_code_lut, save_hair_strands, write_strand
+from .pmvo_utils import load_strand, map_code_lut, save_hair_strands, write_strand
 from .synth_hair import code_table
 
 COLS = 4                     # visible, on hair, confident, dropped segments; then one column per angle
@@ -45,10 +45,6 @@ def angle_bounds(angles_deg):
     if not 1 <= len(angles) <= MAX_ANGLES or not all(0.0 <= a <= 90.0 for a in angles):
         raise ValueError("between 1 and %d angles within [0, 90] degrees" % MAX_ANGLES)
     return angles, np.array([4096.0 * math.cos(2.0 * (a * (math.pi / 180.0))) for a in angles], np.float64)
-
-
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _load(x):
@@ -109,7 +105,7 @@ def support_counts(strands, camera, planes, bust=None, bust_to_origin=(0.0, 0.0,
     K = int(bounds.shape[0])
     cmin = conf_min_code(conf_threshold)
     table = code_table()
-    L, ctx = _lib.lib(), _ctx_for(device)
+    L, ctx = _lib.lib(), _lib.bare_ctx(device)
     with torch.cuda.device(device):
         st = _lib.stream_ptr()
         ori, conf, mask = (_plane(a, device) for a in planes)
@@ -136,10 +132,10 @@ def support_counts(strands, camera, planes, bust=None, bust_to_origin=(0.0, 0.0,
         t0.record()
         for v in range(V):
             for rows in ([strand] if details is None else [strand, details[v]]):
-                _lib.check(L.mh_support_view(ctx, _hp(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
+                _lib.check(L.mh_support_view(ctx, host_ptr(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
                                              _lib.ptr(depth0[v]), _lib.ptr(ori[v]), _lib.ptr(conf[v]), _lib.ptr(mask[v]), cmin,
-                                             _hp(table), _hp(bounds), K, _lib.ptr(scratch), scratch.numel(), _lib.ptr(rows),
-                                             _lib.ptr(view[v]), _lib.ptr(sil[v]), st), "mh_support_view")
+                                             host_ptr(table), host_ptr(bounds), K, _lib.ptr(scratch), scratch.numel(),
+                                             _lib.ptr(rows), _lib.ptr(view[v]), _lib.ptr(sil[v]), st), "mh_support_view")
         t1.record()
         torch.cuda.current_stream().synchronize()      # (the occluder planes and the scratch are read asynchronously)
         if timing is not None:

@@ -12,7 +12,6 @@ float32 values, + - * / sqrt in a fixed order, integer per-voxel sums.
 `voxelize` writes DIR/Occ3D.mat and DIR/Ori3D.mat, what `python HairGrow.py --name=...` reads.  The kernels are
 csrc/hairvolume.hip.  There is no CPU path."""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -22,18 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import host_ptr
 from .hairmetrics import _flag_counts, scores_from_counts
-from .pmvo_utils import (GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE, _ctx_for, get_ground_truth_3D_occ, get_ground_truth_3D_ori,
+from .pmvo_utils import (GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE, get_ground_truth_3D_occ, get_ground_truth_3D_ori,
                          load_strand, save_ori_occ_mat_sparse)
 
 DEFAULT_THRESHOLDS = ((0, None), (1, None), (1, 30.0), (1, 20.0), (1, 10.0))   # (reach in voxels, degrees or None)
 MAX_PAIRS = 8          # one bit of the flag byte each
 MAX_REACH = 4
 MAX_COUNT = 1 << 29    # samples of one voxel: up to here its six sums convert to float64 exactly
-
-
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _dims(grid_resolution):
@@ -80,14 +76,14 @@ def voxelize_strands(strands, bust_to_origin=(0.0, 0.0, 0.0), voxel_min=VOXEL_MI
     np.cumsum(counts, out=offs[1:])
     L = _lib.lib()
     with torch.cuda.device(device):
-        ctx, st = _ctx_for(device), _lib.stream_ptr()
+        ctx, st = _lib.bare_ctx(device), _lib.stream_ptr()
         pd = torch.from_numpy(pts).to(device)
         od = torch.from_numpy(offs).to(device)
         acc = torch.empty((nvox, 8), dtype=torch.int64, device=device)
         occ = torch.empty(nvox, dtype=torch.uint8, device=device)
         counters = torch.empty(2, dtype=torch.int64, device=device)
-        _lib.check(L.mh_strand_volume_accumulate(ctx, _lib.ptr(pd), _lib.ptr(od), S, n, _hp(bust), _hp(vmin), vs, _hp(dims),
-                                                 sub, _lib.ptr(acc), _lib.ptr(occ), _lib.ptr(counters), st),
+        _lib.check(L.mh_strand_volume_accumulate(ctx, _lib.ptr(pd), _lib.ptr(od), S, n, host_ptr(bust), host_ptr(vmin), vs,
+                                                 host_ptr(dims), sub, _lib.ptr(acc), _lib.ptr(occ), _lib.ptr(counters), st),
                    "mh_strand_volume_accumulate")
         index = torch.empty(nvox, dtype=torch.int32, device=device)
         count = torch.empty(1, dtype=torch.int32, device=device)
@@ -102,7 +98,7 @@ def voxelize_strands(strands, bust_to_origin=(0.0, 0.0, 0.0), voxel_min=VOXEL_MI
         coh = torch.empty(G, dtype=torch.float64, device=device)
         sums = torch.empty((G, 6), dtype=torch.int64, device=device) if return_details else None
         refused = torch.empty(1, dtype=torch.int32, device=device)
-        _lib.check(L.mh_strand_volume_resolve(ctx, _lib.ptr(acc), _lib.ptr(index), G, _hp(dims), _lib.ptr(voxels),
+        _lib.check(L.mh_strand_volume_resolve(ctx, _lib.ptr(acc), _lib.ptr(index), G, host_ptr(dims), _lib.ptr(voxels),
                                               _lib.ptr(ori), _lib.ptr(cnt), _lib.ptr(coh), _lib.ptr(sums), _lib.ptr(refused),
                                               st), "mh_strand_volume_resolve")
         if int(refused.cpu()[0]):
@@ -180,8 +176,8 @@ class _Volume:
         self.ori = torch.from_numpy(o).to(device)
         self.index = torch.empty(int(np.prod(dims.astype(np.int64))), dtype=torch.int32, device=device)
         status = torch.empty(2, dtype=torch.int32, device=device)
-        _lib.check(_lib.lib().mh_volume_index(_ctx_for(device), _lib.ptr(self.voxels), self.n, _hp(dims), _lib.ptr(self.index),
-                                              _lib.ptr(status), _lib.stream_ptr()), "mh_volume_index")
+        _lib.check(_lib.lib().mh_volume_index(_lib.bare_ctx(device), _lib.ptr(self.voxels), self.n, host_ptr(dims),
+                                              _lib.ptr(self.index), _lib.ptr(status), _lib.stream_ptr()), "mh_volume_index")
         outside, twice = (int(s) for s in status.cpu().numpy())
         if outside or twice:
             raise ValueError("a voxel list must be unique and inside the grid: %d voxels outside, %d listed again"
@@ -193,9 +189,9 @@ def _match_dev(q, t, dims, reach, cos2, device):
     if q.n == 0:
         return out
     r, c = np.ascontiguousarray(reach, dtype=np.int32), np.ascontiguousarray(cos2, dtype=np.float64)
-    _lib.check(_lib.lib().mh_volume_match(_ctx_for(device), _lib.ptr(q.voxels), _lib.ptr(q.ori), q.n, _lib.ptr(t.index),
-                                          _lib.ptr(t.ori), _hp(dims), _hp(r), _hp(c), int(r.shape[0]), _lib.ptr(out),
-                                          _lib.stream_ptr()), "mh_volume_match")
+    _lib.check(_lib.lib().mh_volume_match(_lib.bare_ctx(device), _lib.ptr(q.voxels), _lib.ptr(q.ori), q.n, _lib.ptr(t.index),
+                                          _lib.ptr(t.ori), host_ptr(dims), host_ptr(r), host_ptr(c), int(r.shape[0]),
+                                          _lib.ptr(out), _lib.stream_ptr()), "mh_volume_match")
     return out
 
 

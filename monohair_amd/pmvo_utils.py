@@ -267,20 +267,7 @@ def load_colmap_points(path, bbox_min, bust_to_origin, vsize=0.005, grid_resolut
 
 
 # ----------------------------------------------------------------------------------------- consensus (HIP)
-def _ctx_for(device):
-    """A bare library context for kernels that need no views (medoid, Gabor)."""
-    import ctypes
-
-    key = str(device)
-    if key not in _ctx_for.cache:
-        h = ctypes.c_void_p()
-        idx = torch.device(device).index or 0
-        _lib.check(_lib.lib().mh_ctx_create(idx, ctypes.byref(h)), "mh_ctx_create")
-        _ctx_for.cache[key] = h
-    return _ctx_for.cache[key]
-
-
-_ctx_for.cache = {}
+_ctx_for = _lib.bare_ctx          # (the name tests and tools import)
 
 
 def compute_points_similarity(ori, return_index=False):
@@ -292,7 +279,7 @@ def compute_points_similarity(ori, return_index=False):
     out = torch.empty((N, 3), dtype=torch.float32, device=ori.device)
     idx = torch.empty((N,), dtype=torch.int32, device=ori.device)
     with torch.cuda.device(ori.device):
-        _lib.check(_lib.lib().mh_medoid_dense(_ctx_for(ori.device), _lib.ptr(ori), N, K, _lib.ptr(out), _lib.ptr(idx),
+        _lib.check(_lib.lib().mh_medoid_dense(_lib.bare_ctx(ori.device), _lib.ptr(ori), N, K, _lib.ptr(out), _lib.ptr(idx),
                                               _lib.stream_ptr()), "mh_medoid_dense")
     return (out, idx) if return_index else out
 
@@ -317,7 +304,7 @@ class GridKNN:
         if self.M:
             box = torch.empty(6, dtype=torch.float32, device=self.device)
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().mh_points_bbox(_ctx_for(self.device), _lib.ptr(self._raw), self.M, _lib.ptr(box),
+                _lib.check(_lib.lib().mh_points_bbox(_lib.bare_ctx(self.device), _lib.ptr(self._raw), self.M, _lib.ptr(box),
                                                      _lib.stream_ptr()), "mh_points_bbox")
             box = box.cpu().numpy()
             self._lo, self._hi = box[:3].copy(), box[3:].copy()
@@ -355,11 +342,9 @@ class GridKNN:
                 np.maximum(dims, 1).astype(np.int32))
 
     def _build(self, grid, dims, pts_sorted, order, start, nocc):
-        import ctypes
-
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mh_grid_build(
-                _ctx_for(self.device), grid.ctypes.data_as(ctypes.c_void_p), dims.ctypes.data_as(ctypes.c_void_p),
+                _lib.bare_ctx(self.device), _lib.host_ptr(grid), _lib.host_ptr(dims),
                 _lib.ptr(self._raw), self.M, _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(pts_sorted),
                 _lib.ptr(order), _lib.ptr(start), _lib.ptr(nocc), _lib.stream_ptr()), "mh_grid_build")
 
@@ -378,8 +363,6 @@ class GridKNN:
         return self._grids[h]
 
     def _run(self, h, q, k, perm=None, valid=None, zero=False):
-        import ctypes
-
         grid, dims, pts, order, start = self._grid(h)
         Q = q.shape[0]
         # (zero: rows of queries the kernel does not finish stay valid indices -- a caller that reads the table before it has
@@ -387,8 +370,8 @@ class GridKNN:
         out = (torch.zeros if zero else torch.empty)((Q, k), dtype=torch.int32, device=self.device)
         status = torch.empty((Q,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mh_knn_grid(_ctx_for(self.device), grid.ctypes.data_as(ctypes.c_void_p),
-                                              dims.ctypes.data_as(ctypes.c_void_p), _lib.ptr(pts), _lib.ptr(order),
+            _lib.check(_lib.lib().mh_knn_grid(_lib.bare_ctx(self.device), _lib.host_ptr(grid),
+                                              _lib.host_ptr(dims), _lib.ptr(pts), _lib.ptr(order),
                                               _lib.ptr(start), _lib.ptr(q), 1 if q.dtype == torch.float64 else 0, Q, k,
                                               1, _lib.ptr(perm), _lib.ptr(valid), _lib.ptr(out), _lib.ptr(status),
                                               _lib.stream_ptr()),
@@ -494,8 +477,6 @@ def spatial_order(points_dev, cell=0.005, half_extent=2.56):
     +-`half_extent`: 1024^3 cells at the defaults; points outside are clamped into the border cells) -> int32 [M] permutation on
     the device (mh_grid_build: cell keys + one radix sort; nothing is read back).  Only the ORDER in which a kernel takes the
     rows depends on it (mh_filter_points_ordered): 64 consecutive entries are spatial neighbours."""
-    import ctypes
-
     dev = points_dev.device
     M = int(points_dev.shape[0])
     order = torch.empty(M, dtype=torch.int32, device=dev)
@@ -507,7 +488,7 @@ def spatial_order(points_dev, cell=0.005, half_extent=2.56):
     dims = np.array([n, n, n], dtype=np.int32)
     scratch = torch.empty(int(L.mh_grid_scratch_bytes(M)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(L.mh_grid_build(_ctx_for(dev), grid.ctypes.data_as(ctypes.c_void_p), dims.ctypes.data_as(ctypes.c_void_p),
+        _lib.check(L.mh_grid_build(_lib.bare_ctx(dev), _lib.host_ptr(grid), _lib.host_ptr(dims),
                                    _lib.ptr(points_dev), M, _lib.ptr(scratch), scratch.numel(), None, _lib.ptr(order), None,
                                    None, _lib.stream_ptr()), "mh_grid_build")
     return order
@@ -535,8 +516,6 @@ def voxel_fit(select_points, select_ori, device, voxel_min=VOXEL_MIN, voxel_size
     Returns dict(voxels [G,3] int64 (x,y,z), ori [G,3] f32) and, with dense=True, occ [X,Y,Z] / ori [X,Y,Z,3]
     float64 numpy arrays as the reference builds them.  The inputs are NOT modified (the reference flips them in place,
     PMVO.py:697-698 and p2v; nothing reads them afterwards)."""
-    import ctypes
-
     g = np.asarray(grid_resolution).astype(np.int64)
     dev = torch.device(device)
     pts = np.ascontiguousarray(select_points).reshape(-1, 3)
@@ -554,9 +533,9 @@ def voxel_fit(select_points, select_ori, device, voxel_min=VOXEL_MIN, voxel_size
         vmin = np.ascontiguousarray(voxel_min, dtype=np.float64)
         dims = np.ascontiguousarray(g, dtype=np.int32)
         with torch.cuda.device(dev):
-            _lib.check(L.mh_voxel_group(_ctx_for(dev), _lib.ptr(pd), 1 if pts.dtype == np.float64 else 0, _lib.ptr(od), n,
-                                        vmin.ctypes.data_as(ctypes.c_void_p), float(voxel_size),
-                                        dims.ctypes.data_as(ctypes.c_void_p), _lib.ptr(scratch), scratch.numel(),
+            _lib.check(L.mh_voxel_group(_lib.bare_ctx(dev), _lib.ptr(pd), 1 if pts.dtype == np.float64 else 0, _lib.ptr(od), n,
+                                        _lib.host_ptr(vmin), float(voxel_size),
+                                        _lib.host_ptr(dims), _lib.ptr(scratch), scratch.numel(),
                                         _lib.ptr(ks_d), _lib.ptr(order_d), _lib.ptr(o), _lib.stream_ptr()),
                        "mh_voxel_group")
         ks = ks_d.cpu().numpy()
@@ -571,7 +550,7 @@ def voxel_fit(select_points, select_ori, device, voxel_min=VOXEL_MIN, voxel_size
     med = torch.empty((G, 3), dtype=torch.float32, device=dev)
     if G:
         with torch.cuda.device(dev):
-            _lib.check(L.mh_medoid_segmented(_ctx_for(dev), _lib.ptr(o), _lib.ptr(seg), G, max_group,
+            _lib.check(L.mh_medoid_segmented(_lib.bare_ctx(dev), _lib.ptr(o), _lib.ptr(seg), G, max_group,
                                              _lib.ptr(med), None, _lib.stream_ptr()), "mh_medoid_segmented")
     kv = ks[starts] if G else np.zeros(0, np.int64)
     vox = torch.from_numpy(np.stack([kv // (int(g[1]) * int(g[2])), (kv // int(g[2])) % int(g[1]), kv % int(g[2])],
@@ -592,15 +571,13 @@ def voxel_fit_device(pts_dev, ori_dev, n, device, voxel_min=VOXEL_MIN, voxel_siz
     keys + stable sort + canonicalised gather (mh_voxel_group), run boundaries on the device (mh_segment_heads), one
     segmented-medoid launch; the host reads two counters in between and the G voxel keys + orientations at the end.
     -> (voxels [G,3] int64 (x,y,z) ascending, ori [G,3] float32) numpy arrays -- the same values as voxel_fit."""
-    import ctypes
-
     g = np.asarray(grid_resolution).astype(np.int64)
     dev = torch.device(device)
     n = int(n)
     if n == 0:
         return np.zeros((0, 3), np.int64), np.zeros((0, 3), np.float32)
     L = _lib.lib()
-    ctx = _ctx_for(dev)
+    ctx = _lib.bare_ctx(dev)
     ks_d = torch.empty(n, dtype=torch.int64, device=dev)
     order_d = torch.empty(n, dtype=torch.int32, device=dev)
     o = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -613,8 +590,8 @@ def voxel_fit_device(pts_dev, ori_dev, n, device, voxel_min=VOXEL_MIN, voxel_siz
     dims = np.ascontiguousarray(g, dtype=np.int32)
     with torch.cuda.device(dev):
         st = _lib.stream_ptr()
-        _lib.check(L.mh_voxel_group(ctx, _lib.ptr(pts_dev), 0, _lib.ptr(ori_dev), n, vmin.ctypes.data_as(ctypes.c_void_p),
-                                    float(voxel_size), dims.ctypes.data_as(ctypes.c_void_p), _lib.ptr(scratch),
+        _lib.check(L.mh_voxel_group(ctx, _lib.ptr(pts_dev), 0, _lib.ptr(ori_dev), n, _lib.host_ptr(vmin),
+                                    float(voxel_size), _lib.host_ptr(dims), _lib.ptr(scratch),
                                     scratch.numel(), _lib.ptr(ks_d), _lib.ptr(order_d), _lib.ptr(o), st), "mh_voxel_group")
         _lib.check(L.mh_segment_heads(ctx, _lib.ptr(ks_d), n, _lib.ptr(seg), _lib.ptr(heads), _lib.ptr(meta),
                                       _lib.ptr(sel_scratch), sel_scratch.numel(), st), "mh_segment_heads")
@@ -678,13 +655,11 @@ def _mat5_prefix(name, dims):
 
 def _write_mat_sparse(fname, name, dims, idx, val, threads):
     """one MAT-v5 file holding the float64 array `name` of shape `dims`: zero but for val at the element indices idx"""
-    import ctypes
-
     prefix, ndata = _mat5_prefix(name, dims)
     idx = np.ascontiguousarray(idx, dtype=np.int64)
     val = np.ascontiguousarray(val, dtype=np.float64)
-    _lib.check(_lib.lib().mh_mat_write_sparse(fname.encode(), prefix, len(prefix), ndata, idx.ctypes.data_as(ctypes.c_void_p),
-                                              val.ctypes.data_as(ctypes.c_void_p), len(idx), threads), "mh_mat_write_sparse")
+    _lib.check(_lib.lib().mh_mat_write_sparse(fname.encode(), prefix, len(prefix), ndata, _lib.host_ptr(idx),
+                                              _lib.host_ptr(val), len(idx), threads), "mh_mat_write_sparse")
 
 
 def save_ori_occ_mat_sparse(path, grid_resolution, voxels, ori, threads=1):
@@ -759,7 +734,7 @@ class SparseMatWriter:
                 if lin is not None and len(lin):
                     idx = lin if k == 0 else (lin[None, :] + (Y * X * Z) * np.arange(3, dtype=np.int64)[:, None]).reshape(-1)
                     idx = np.ascontiguousarray(idx, dtype=np.int64)
-                    self._L.mh_mat_sparse_touch(h, idx.ctypes.data_as(ctypes.c_void_p), len(idx))
+                    self._L.mh_mat_sparse_touch(h, _lib.host_ptr(idx), len(idx))
             except BaseException as e:
                 self._error.append(e)
 
@@ -784,7 +759,6 @@ class SparseMatWriter:
     _TMP = ".writing"
 
     def finish(self, voxels, ori):
-        import ctypes
         import threading
 
         import time
@@ -815,7 +789,7 @@ class SparseMatWriter:
             # coherent); unmapping 400 MB of dirty pages and closing (1-2 ms) finish behind its back
             try:
                 _lib.check(self._L.mh_mat_sparse_store_voxels(
-                    h, v.ctypes.data_as(ctypes.c_void_p), None if val is None else val.ctypes.data_as(ctypes.c_void_p),
+                    h, _lib.host_ptr(v), None if val is None else _lib.host_ptr(val),
                     int(val is not None and val.dtype == np.float64), len(v), X, Y, Z), "mh_mat_sparse_store_voxels")
             except BaseException as e:
                 err.append(e)

@@ -11,7 +11,6 @@ returns a [V,H,W] tensor that `PMVO.from_planes` / `PMVO.from_u8` take as is.  T
 specification and are pinned against a real OpenGL implementation (SwiftShader) up to what GL leaves to the driver
 (sub-pixel snapping, interpolation rounding; docs/HISTORY.md §4.9, §4.10).
 """
-import ctypes
 import os
 
 import numpy as np
@@ -19,7 +18,7 @@ import torch
 
 from . import _lib
 from .camera import camera_records, load_cam, parsing_camera
-from .pmvo_utils import _ctx_for, read_obj
+from .pmvo_utils import read_obj
 
 BUST_TO_ORIGIN = np.array([0.006, -1.644, 0.010])      # Render_utils.py:312
 
@@ -41,7 +40,7 @@ class DepthRenderer:
         self.verts = torch.from_numpy(np.concatenate(verts) if verts else np.zeros((0, 3), np.float32)).to(self.device)
         self.faces = torch.from_numpy(np.concatenate(faces) if faces else np.zeros((0, 3), np.int32)).to(self.device)
         self._L = _lib.lib()
-        self._ctx = _ctx_for(self.device)
+        self._ctx = _lib.bare_ctx(self.device)
         self._scratch = None
 
     def render(self, cam_record, H, W, pixel_center=0.5, out=None, channels=1):
@@ -56,7 +55,7 @@ class DepthRenderer:
         assert out.is_contiguous() and out.numel() == H * W * channels and out.dtype == torch.float32
         rec = np.ascontiguousarray(cam_record, dtype=np.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.mh_render_depth(self._ctx, rec.ctypes.data_as(ctypes.c_void_p), _lib.ptr(self.verts), Nv,
+            _lib.check(self._L.mh_render_depth(self._ctx, _lib.host_ptr(rec), _lib.ptr(self.verts), Nv,
                                                _lib.ptr(self.faces), Nf, H, W, float(pixel_center),
                                                _lib.ptr(self._scratch), need, _lib.ptr(out), channels,
                                                _lib.stream_ptr()), "mh_render_depth")
@@ -141,7 +140,7 @@ class StrandRenderer:
         self.verts = torch.from_numpy(np.asarray(vertices, dtype=np.float64).reshape(-1, 3).astype(np.float32)).to(self.device)
         self.faces = torch.from_numpy(np.asarray(faces, dtype=np.int64).reshape(-1, 3).astype(np.int32)).to(self.device)
         self._L = _lib.lib()
-        self._ctx = _ctx_for(self.device)
+        self._ctx = _lib.bare_ctx(self.device)
         self._scratch = None
 
     def render(self, cam_record, H, W, color_option, depth_option, clear, draw_strands=True, pixel_center=0.5, out=None,
@@ -161,7 +160,7 @@ class StrandRenderer:
             _lib.check(self._L.mh_ctx_set_option(self._ctx, b"line_rule", int(line_rule)), "line_rule")
             try:
                 _lib.check(self._L.mh_render_strands(
-                    self._ctx, rec.ctypes.data_as(ctypes.c_void_p), _lib.ptr(self.verts), Nv, _lib.ptr(self.faces), Nf,
+                    self._ctx, _lib.host_ptr(rec), _lib.ptr(self.verts), Nv, _lib.ptr(self.faces), Nf,
                     _lib.ptr(self.line_pts), _lib.ptr(self.line_tan), self.nseg, H, W, float(pixel_center), width,
                     int(color_option) if draw_strands else -1, int(depth_option), float(clear), _lib.ptr(self._scratch),
                     need, _lib.ptr(out), _lib.stream_ptr()), "mh_render_strands")

@@ -8,7 +8,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pmvo_utils import _ctx_for
 
 
 def strand_offsets(lens):
@@ -50,7 +49,7 @@ def smooth_strands(strands, lap_constraint=2.0, pos_constraint=1.0, fix_tips=Fal
     offs_d = torch.from_numpy(offs).to(dev)
     work = torch.empty((3 * int(offs[-1]),), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mh_smooth_strands(_ctx_for(dev), _lib.ptr(pts), _lib.ptr(offs_d), len(arrs),
+        _lib.check(_lib.lib().mh_smooth_strands(_lib.bare_ctx(dev), _lib.ptr(pts), _lib.ptr(offs_d), len(arrs),
                                                 float(lap_constraint), float(pos_constraint), _lib.ptr(work),
                                                 _lib.stream_ptr()), "mh_smooth_strands")
     for i, (a, x) in enumerate(zip(arrs, split_strands(pts.cpu().numpy(), offs))):

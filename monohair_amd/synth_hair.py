@@ -19,7 +19,6 @@ header, restated by tests/hair_photo_np.py): capture_images/ holds shaded, anti-
 best_ori/ and conf/ are what the Gabor stage makes of them.  There is no CPU path for the renderer; the strand model is host
 code (numpy, libm: the same arrays for the same seed on one host, not bit for bit between hosts)."""
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -29,8 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib, synth
+from ._lib import host_ptr
 from .camera import camera_records, cameras_from_list
-from .pmvo_utils import _ctx_for, load_strand, read_obj, write_strand
+from .pmvo_utils import load_strand, read_obj, write_strand
 
 HEAD_R = 0.10          # the scalp sphere of synth.write_case (scalp_tsfm.obj)
 BUST_R = 0.09          # its bust sphere (bust_long_tsfm.obj)
@@ -115,10 +115,6 @@ def _strands(strands):
     return counts, offs, points
 
 
-def _hp(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device="cuda:0", return_details=False,
                    n_full=None, pixel_center=0.0):
     """strands = (counts, points); camera: dict view -> Camera (or [V,48] camera records) -> device tensors (depth float32
@@ -135,7 +131,7 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
     recs = np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
     V = recs.shape[0]
     table = code_table()
-    L, ctx = _lib.lib(), _ctx_for(device)
+    L, ctx = _lib.lib(), _lib.bare_ctx(device)
     with torch.cuda.device(device):
         st = _lib.stream_ptr()
         pts = torch.from_numpy(pts_h).to(device)
@@ -156,8 +152,8 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
             d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
             out = (_lib.ptr(depth[v]), _lib.ptr(ori[v]), _lib.ptr(conf[v]), _lib.ptr(mask[v]))
             if not return_details:
-                _lib.check(L.mh_capture_view(ctx, _hp(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
-                                             n_full, _lib.ptr(d0), _hp(table), _lib.ptr(scratch), scratch.numel(), *out, st),
+                _lib.check(L.mh_capture_view(ctx, host_ptr(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
+                                             n_full, _lib.ptr(d0), host_ptr(table), _lib.ptr(scratch), scratch.numel(), *out, st),
                            "mh_capture_view")
                 continue
             vert = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
@@ -166,7 +162,7 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
             cnt = torch.empty((H, W), dtype=torch.int32, device=device)
             c2, s2 = (torch.empty((H, W), dtype=torch.int64, device=device) for _ in range(2))
             dropped = torch.empty(1, dtype=torch.int32, device=device)
-            _lib.check(L.mh_capture_project(ctx, _hp(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
+            _lib.check(L.mh_capture_project(ctx, host_ptr(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
                        "mh_capture_project")
             _lib.check(L.mh_capture_zmin(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, H, W, radius,
                                          _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(dropped), st), "mh_capture_zmin")
@@ -174,7 +170,7 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
                                                float(tol), _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2),
                                                _lib.ptr(s2), st), "mh_capture_accumulate")
             _lib.check(L.mh_capture_resolve(ctx, _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2), _lib.ptr(s2), _lib.ptr(d0),
-                                            _hp(table), n_full, H, W, *out, st), "mh_capture_resolve")
+                                            host_ptr(table), n_full, H, W, *out, st), "mh_capture_resolve")
             details.append(dict(vert=vert[:n], valid=valid[:n], zmin=zmin, cnt=cnt, c2=c2, s2=s2, dropped=int(dropped.item()),
                                 depth0=d0))
         torch.cuda.current_stream().synchronize()      # (the occluder plane and the scratch are read asynchronously)
@@ -225,7 +221,7 @@ def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHO
     light_h = np.ascontiguousarray(light_directions(recs) if light is None else light, dtype=np.float64).reshape(-1, 3)
     if light_h.shape[0] != V:
         raise ValueError("light: one direction per view")
-    L, ctx = _lib.lib(), _ctx_for(device)
+    L, ctx = _lib.lib(), _lib.bare_ctx(device)
     need = int(L.mh_photo_scratch_bytes(n, H, W, ss))
     if need == 0:
         raise ValueError("photo_planes: supersample in {1, 2, 4, 8} and supersample^2 * H * W < 2^31")
@@ -245,8 +241,8 @@ def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHO
         for v in range(V):
             d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
             if not return_details:
-                _lib.check(L.mh_photo_view(ctx, _hp(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, _lib.ptr(alb),
-                                           _hp(light_h[v]), float(ambient), H, W, ss, width, _lib.ptr(d0), int(bust_code),
+                _lib.check(L.mh_photo_view(ctx, host_ptr(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, _lib.ptr(alb),
+                                           host_ptr(light_h[v]), float(ambient), H, W, ss, width, _lib.ptr(d0), int(bust_code),
                                            int(background_code), _lib.ptr(scratch), scratch.numel(), _lib.ptr(gray[v]), None,
                                            st), "mh_photo_view")
                 continue
@@ -256,10 +252,10 @@ def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHO
             keys = torch.empty((ss * H, ss * W), dtype=torch.int64, device=device)
             cover = torch.empty((H, W), dtype=torch.int32, device=device)
             dropped = torch.empty(1, dtype=torch.int32, device=device)
-            _lib.check(L.mh_capture_project(ctx, _hp(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
+            _lib.check(L.mh_capture_project(ctx, host_ptr(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
                        "mh_capture_project")
             _lib.check(L.mh_photo_shade(ctx, _lib.ptr(pts), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(alb),
-                                        _hp(light_h[v]), float(ambient), _lib.ptr(shade), st), "mh_photo_shade")
+                                        host_ptr(light_h[v]), float(ambient), _lib.ptr(shade), st), "mh_photo_shade")
             _lib.check(L.mh_photo_front(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(shade), H, W, ss,
                                         width, _lib.ptr(d0), _lib.ptr(keys), _lib.ptr(dropped), st), "mh_photo_front")
             _lib.check(L.mh_photo_resolve(ctx, _lib.ptr(keys), _lib.ptr(d0), H, W, ss, int(bust_code), int(background_code),

@@ -166,7 +166,8 @@ def test_ball_of_a_start_on_a_cell_face(setup, cells):
     from scipy.spatial import KDTree
 
     from monohair_amd import _lib
-    from monohair_amd.hairgrow import _hp, grid_dims
+    from monohair_amd._lib import host_ptr as _hp
+    from monohair_amd.hairgrow import grid_dims
     from monohair_amd.strand_smooth import pack_strands
 
     _, _, hg, _, _, vox = setup

@@ -3,7 +3,7 @@ launches of the smoothing chain, and the background writer of refine/*.npy.  No 
 import numpy as np
 import pytest
 
-from monohair_amd.pmvo import _Writer, _chunk_slices, _loss_groups, _row_offsets
+from monohair_amd.refine import _Writer, _chunk_slices, _loss_groups, _row_offsets
 
 SIZES = (1, 4999, 5000, 5001, 10000, 16901)
 RANKS = (1, 2, 3, 7)
@@ -149,7 +149,7 @@ def test_a_process_that_fails_without_joining_the_writer_still_ends(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys; sys.path.insert(0, %r)\n"
             "import numpy as np\n"
-            "from monohair_amd.pmvo import _Writer\n"
+            "from monohair_amd.refine import _Writer\n"
             "w = _Writer()\n"
             "w.save((%r, np.arange(5)))\n"
             "raise RuntimeError('after save, before join')\n") % (root, str(tmp_path / "queued.npy"))

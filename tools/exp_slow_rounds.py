@@ -98,7 +98,7 @@ if os.environ.get("EXP_ROUNDS"):
             top = sorted(calls)[-3:]
             print("  slow round %d: %d it/s; enqueue %.1f ms, drain %.1f ms; slowest calls (ms) %s; ring %s" % (
                 rd, r[-1], (t1 - t0) * 1e3, (t2 - t1) * 1e3, [round(x * 1e3, 2) for x in top],
-                [v["i"] for v in pm._stage.values()]))
+                [v["i"] for v in pm.transfer._rings.values()]))
     print({"allowed": len(os.sched_getaffinity(0)), "gc": os.environ.get("EXP_GC", "1"), "rounds": r, "end": (nda, nha)})
     sys.exit(0)
 res = {}
