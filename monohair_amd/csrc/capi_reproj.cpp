@@ -3,17 +3,15 @@
 
 #include "mh_capi.h"
 
-#define MH_SUP_MAX_RADIUS 16
+// scratch of mh_support_view: the shared front (mh_capi.h) | zmin
+struct SupportScratch : ViewScratch {
+    float *zmin;
+    SupportScratch(int n, int H, int W, void *base) : ViewScratch(n, base) { zmin = take<float>((size_t)H * W * 4); }
+};
 
-static size_t sup_align(size_t b) { return (b + 255) / 256 * 256; }
-
-static bool sup_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
-
-// scratch of mh_support_view: dropped 256 B | vert | valid | zmin
 extern "C" size_t mh_support_scratch_bytes(int n_points, int H, int W) {
-    if (n_points < 0 || !sup_image_ok(H, W)) return 0;
-    const size_t n = (size_t)(n_points > 0 ? n_points : 1), npix = (size_t)H * W;
-    return 256 + sup_align(n * 12) + sup_align(n) + sup_align(npix * 4);
+    if (n_points < 0 || !image_fits_int32(H, W)) return 0;
+    return SupportScratch(n_points, H, W, nullptr).bytes;
 }
 
 extern "C" int mh_support_accumulate(mh_ctx *ctx, const float *vert, const uint8_t *valid, const long long *offsets,
@@ -21,9 +19,9 @@ extern "C" int mh_support_accumulate(mh_ctx *ctx, const float *vert, const uint8
                                      const float *zmin, const uint8_t *ori_u8, const uint8_t *conf_u8, const uint8_t *mask_u8,
                                      int conf_min_code, const float *table_host, const double *bounds_host, int n_bounds,
                                      long long *strand_counts, long long *view_counts, void *stream) {
-    if (!ctx || !zmin || !ori_u8 || !conf_u8 || !mask_u8 || !table_host || !bounds_host || !view_counts || n_strands < 0 ||
-        n_points < 0 || (n_points > 0 && (!vert || !valid || !offsets || n_strands < 1 || !strand_counts)) ||
-        !sup_image_ok(H, W) || !(tol >= 0.0f) || n_bounds < 1 || n_bounds > MH_SUP_MAX_BOUNDS || conf_min_code < 0 ||
+    if (!ctx || !zmin || !ori_u8 || !conf_u8 || !mask_u8 || !table_host || !bounds_host || !view_counts ||
+        !strands_ok(vert, valid, offsets, n_strands, n_points) || (n_points > 0 && !strand_counts) ||
+        !image_fits_int32(H, W) || !(tol >= 0.0f) || n_bounds < 1 || n_bounds > MH_SUP_MAX_BOUNDS || conf_min_code < 0 ||
         conf_min_code > 256)
         return fail(MH_ERR_ARG, "mh_support_accumulate: bad arguments");
     MhCapTable tab;
@@ -42,7 +40,7 @@ extern "C" int mh_support_accumulate(mh_ctx *ctx, const float *vert, const uint8
 
 extern "C" int mh_support_silhouette(mh_ctx *ctx, const float *zmin, const uint8_t *mask_u8, int H, int W,
                                      long long *silhouette, void *stream) {
-    if (!ctx || !zmin || !mask_u8 || !silhouette || !sup_image_ok(H, W))
+    if (!ctx || !zmin || !mask_u8 || !silhouette || !image_fits_int32(H, W))
         return fail(MH_ERR_ARG, "mh_support_silhouette: bad arguments");
     MH_HIP(hipSetDevice(ctx->device));
     return launched(mh_launch_support_silhouette(zmin, mask_u8, H, W, (unsigned long long *)silhouette, (hipStream_t)stream),
@@ -55,24 +53,20 @@ extern "C" int mh_support_view(mh_ctx *ctx, const float *cam_host, const float *
                                const float *table_host, const double *bounds_host, int n_bounds, void *scratch,
                                size_t scratch_bytes, long long *strand_counts, long long *view_counts, long long *silhouette,
                                void *stream) {
-    if (!ctx || !scratch || n_points < 0 || !sup_image_ok(H, W) || (n_points > 0 && !points) || radius < 0 ||
-        radius > MH_SUP_MAX_RADIUS)
+    if (!ctx || !scratch || n_points < 0 || !image_fits_int32(H, W) || (n_points > 0 && !points) || radius < 0 ||
+        radius > MH_MAX_RADIUS)
         return fail(MH_ERR_ARG, "mh_support_view: bad arguments");
     const size_t need = mh_support_scratch_bytes(n_points, H, W);
     if (scratch_bytes < need) return fail(MH_ERR_ARG, "mh_support_view: scratch too small (%zu < %zu)", scratch_bytes, need);
-    const size_t n = (size_t)(n_points > 0 ? n_points : 1);
-    char *base = (char *)scratch;
-    int32_t *dropped = (int32_t *)base;
-    float *vert = (float *)(base += 256);
-    uint8_t *valid = (uint8_t *)(base += sup_align(n * 12));
-    float *zmin = (float *)(base += sup_align(n));
-    int rc = mh_capture_project(ctx, cam_host, points, n_points, H, W, vert, valid, stream);
+    const SupportScratch s(n_points, H, W, scratch);
+    int rc = mh_capture_project(ctx, cam_host, points, n_points, H, W, s.vert, s.valid, stream);
     if (rc == MH_OK)
-        rc = mh_capture_zmin(ctx, vert, valid, offsets, n_strands, n_points, H, W, radius, depth0, zmin, dropped, stream);
+        rc = mh_capture_zmin(ctx, s.vert, s.valid, offsets, n_strands, n_points, H, W, radius, depth0, s.zmin, s.dropped,
+                             stream);
     if (rc == MH_OK)
-        rc = mh_support_accumulate(ctx, vert, valid, offsets, n_strands, n_points, H, W, tol, depth0, zmin, ori_u8, conf_u8,
-                                   mask_u8, conf_min_code, table_host, bounds_host, n_bounds, strand_counts, view_counts,
-                                   stream);
-    if (rc == MH_OK) rc = mh_support_silhouette(ctx, zmin, mask_u8, H, W, silhouette, stream);
+        rc = mh_support_accumulate(ctx, s.vert, s.valid, offsets, n_strands, n_points, H, W, tol, depth0, s.zmin, ori_u8,
+                                   conf_u8, mask_u8, conf_min_code, table_host, bounds_host, n_bounds, strand_counts,
+                                   view_counts, stream);
+    if (rc == MH_OK) rc = mh_support_silhouette(ctx, s.zmin, mask_u8, H, W, silhouette, stream);
     return rc;
 }

@@ -6,22 +6,30 @@
 
 static bool vol_dims_ok(const int32_t *dims) { return dims && cells_fit_int32(dims[0], dims[1], dims[2]); }
 
+// the one place that fills an MhVolGrid; bust_to_origin: null = no shift.  false: an argument is missing or not usable
+static bool vol_grid(MhVolGrid *gr, const double *voxel_min, double voxel_size, const int32_t *dims,
+                     const double *bust_to_origin = nullptr) {
+    if (!voxel_min || !vol_dims_ok(dims) || !(voxel_size > 0.0 && std::isfinite(voxel_size))) return false;
+    for (int c = 0; c < 3; ++c) {
+        gr->bust[c] = bust_to_origin ? bust_to_origin[c] : 0.0, gr->vmin[c] = voxel_min[c];
+        if (!std::isfinite(gr->bust[c]) || !std::isfinite(voxel_min[c])) return false;
+    }
+    gr->vs = voxel_size;
+    gr->X = dims[0], gr->Y = dims[1], gr->Z = dims[2];
+    return true;
+}
+
 extern "C" int mh_strand_volume_accumulate(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands,
                                            int n_points, const double *bust_to_origin, const double *voxel_min,
                                            double voxel_size, const int32_t *dims, int sub, long long *acc, uint8_t *occ,
                                            long long *counters, void *stream) {
-    if (!ctx || !bust_to_origin || !voxel_min || !vol_dims_ok(dims) || !acc || !occ || !counters || n_strands < 0 ||
-        n_points < 0 || (n_points > 0 && (!points || !offsets || n_strands < 1)) || sub < 1 || sub > 16 ||
+    if (!ctx || !bust_to_origin || !voxel_min || !vol_dims_ok(dims) || !acc || !occ || !counters ||
+        !strands_ok(points, nullptr, offsets, n_strands, n_points, /*has_valid=*/false) || sub < 1 || sub > 16 ||
         !(voxel_size > 0.0 && std::isfinite(voxel_size)))
         return fail(MH_ERR_ARG, "mh_strand_volume_accumulate: bad arguments");
-    MhVolGrid gr;
-    for (int c = 0; c < 3; ++c) {
-        if (!std::isfinite(bust_to_origin[c]) || !std::isfinite(voxel_min[c]))
-            return fail(MH_ERR_ARG, "mh_strand_volume_accumulate: bust_to_origin and voxel_min must be finite");
-        gr.bust[c] = bust_to_origin[c], gr.vmin[c] = voxel_min[c];
-    }
-    gr.vs = voxel_size;
-    gr.X = dims[0], gr.Y = dims[1], gr.Z = dims[2];
+    MhVolGrid gr;      // (what is left for vol_grid to refuse here is a value that is not finite)
+    if (!vol_grid(&gr, voxel_min, voxel_size, dims, bust_to_origin))
+        return fail(MH_ERR_ARG, "mh_strand_volume_accumulate: bust_to_origin and voxel_min must be finite");
     MH_HIP(hipSetDevice(ctx->device));
     return launched(mh_launch_strand_volume_accum(points, (const int64_t *)offsets, n_strands, n_points, gr, sub,
                                                   (unsigned long long *)acc, occ, (unsigned long long *)counters,
@@ -73,17 +81,6 @@ extern "C" int mh_volume_match(mh_ctx *ctx, const long long *q_voxels, const flo
 }
 
 // ---- the inner fill (csrc/hairfill.hip; include/mh_pmvo.h, "Inner fill")
-static bool vol_grid(MhVolGrid *gr, const double *voxel_min, double voxel_size, const int32_t *dims) {
-    if (!voxel_min || !vol_dims_ok(dims) || !(voxel_size > 0.0 && std::isfinite(voxel_size))) return false;
-    for (int c = 0; c < 3; ++c) {
-        if (!std::isfinite(voxel_min[c])) return false;
-        gr->bust[c] = 0.0, gr->vmin[c] = voxel_min[c];
-    }
-    gr->vs = voxel_size;
-    gr->X = dims[0], gr->Y = dims[1], gr->Z = dims[2];
-    return true;
-}
-
 extern "C" int mh_inner_votes(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
                               int32_t *counts, void *stream) {
     if (!ctx || !ctx->rec || !ctx->mask || !ctx->cams || ctx->V < 1) return fail(MH_ERR_STATE, "mh_inner_votes: views not set");

@@ -15,7 +15,6 @@
 // 8-bit gray images on an S x S supersampled grid, with the vertex step above it and the strand lookup and the segment walk of
 // mh_hairwalk.h (shared with csrc/hairreproj.hip):
 //   mh_photo_shade_kernel       one lane per segment: the Kajiya-Kay diffuse shade q of the world segment, 0..255
-//   mh_photo_fill_kernel        the key plane set to all ones
 //   mh_photo_front_kernel       one lane per segment: atomicMin of (bits(zf) << 32 | q) on every sub-pixel of its fragments
 //   mh_photo_resolve_kernel     one lane per pixel: the S^2 keys of its sub-pixels -> gray, cover
 //
@@ -26,7 +25,8 @@
 #include <stdint.h>
 
 #include "mh_device.h"
-#include "mh_hairwalk.h"      // the strand lookup and the segment walk
+#include "mh_fill.h"
+#include "mh_hairwalk.h"      // the segment walk and, with mh_strands.h, the strand lookup
 
 __global__ __launch_bounds__(256) void mh_capture_project_kernel(MhCapCam cam, const float *__restrict__ pts, int n, float Hf,
                                                                  float Wf, float *__restrict__ vert,
@@ -41,11 +41,6 @@ __global__ __launch_bounds__(256) void mh_capture_project_kernel(MhCapCam cam, c
     vert[3 * (size_t)i + 2] = (-z / 2.0f) * 255.0f;
     // (NaN fails every comparison: an invalid vertex)
     valid[i] = (z < -0.1f && __builtin_fabsf(row) < 1048576.0f && __builtin_fabsf(col) < 1048576.0f) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void mh_capture_fill_kernel(uint32_t *__restrict__ p, uint32_t value, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = value;
 }
 
 // ACCUM = false: pass A (zmin, dropped); true: pass B (cnt, C2, S2)
@@ -129,18 +124,12 @@ extern "C" int mh_launch_capture_project(MhCapCam cam, const float *pts, int n, 
     return (int)hipGetLastError();
 }
 
-static int mh_cap_fill(void *p, uint32_t value, size_t nwords, hipStream_t st) {
-    hipLaunchKernelGGL(mh_capture_fill_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, st, (uint32_t *)p, value,
-                       nwords);
-    return (int)hipGetLastError();
-}
-
 extern "C" int mh_launch_capture_zmin(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points,
                                       int H, int W, int radius, const float *depth0, float *zmin, int32_t *dropped,
                                       hipStream_t st) {
-    int rc = mh_cap_fill(zmin, 0x7f800000u /* +inf */, (size_t)H * W, st);
+    int rc = mh_fill_u32(zmin, 0x7f800000u /* +inf */, (size_t)H * W, st);
     if (rc) return rc;
-    if ((rc = mh_cap_fill(dropped, 0u, 1, st))) return rc;
+    if ((rc = mh_fill_u32(dropped, 0u, 1, st))) return rc;
     if (n_points < 2) return 0;
     hipLaunchKernelGGL(mh_capture_pass_kernel<false>, dim3((n_points - 1 + 255) / 256), dim3(256), 0, st, vert, valid, offs,
                        S, n_points, H, W, radius, 0.0f, depth0, (uint32_t *)zmin, dropped, (int32_t *)nullptr,
@@ -152,10 +141,10 @@ extern "C" int mh_launch_capture_accum(const float *vert, const uint8_t *valid, 
                                        int H, int W, int radius, float tol, const float *depth0, const float *zmin,
                                        int32_t *cnt, long long *C2, long long *S2, hipStream_t st) {
     const size_t npix = (size_t)H * W;
-    int rc = mh_cap_fill(cnt, 0u, npix, st);
+    int rc = mh_fill_u32(cnt, 0u, npix, st);
     if (rc) return rc;
-    if ((rc = mh_cap_fill(C2, 0u, 2 * npix, st))) return rc;
-    if ((rc = mh_cap_fill(S2, 0u, 2 * npix, st))) return rc;
+    if ((rc = mh_fill_u32(C2, 0u, 2 * npix, st))) return rc;
+    if ((rc = mh_fill_u32(S2, 0u, 2 * npix, st))) return rc;
     if (n_points < 2) return 0;
     hipLaunchKernelGGL(mh_capture_pass_kernel<true>, dim3((n_points - 1 + 255) / 256), dim3(256), 0, st, vert, valid, offs, S,
                        n_points, H, W, radius, tol, depth0, (uint32_t *)const_cast<float *>(zmin), (int32_t *)nullptr, cnt,
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(256) void mh_photo_shade_kernel(const float *__rest
                                                              double ambient, uint8_t *__restrict__ shade) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_points) return;
-    const int s = mh_cap_strand_of(offs, S, i);
+    const int s = mh_strand_of(offs, S, i);
     if (s >= S || i + 1 >= offs[s + 1] || !valid[i] || !valid[i + 1]) {
         shade[i] = 0;
         return;
@@ -195,11 +184,6 @@ __global__ __launch_bounds__(256) void mh_photo_shade_kernel(const float *__rest
     if (tt > 0.0) sn = sqrt(fmax(0.0, 1.0 - (tl * tl) / tt));
     const double v = (255.0 * (double)albedo[s]) * (ambient + (1.0 - ambient) * sn);
     shade[i] = v > 0.0 ? (uint8_t)(int)fmin(255.0, rint(v)) : 0;      // (NaN fails the comparison)
-}
-
-__global__ __launch_bounds__(256) void mh_photo_fill_kernel(unsigned long long *__restrict__ p, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = ~0ull;
 }
 
 // ss: the supersampling factor; H, W: the image; the key plane is [ss H, ss W]
@@ -271,11 +255,9 @@ extern "C" int mh_launch_photo_shade(const float *pts, const uint8_t *valid, con
 extern "C" int mh_launch_photo_front(const float *vert, const uint8_t *valid, const int64_t *offs, int S, int n_points,
                                      const uint8_t *shade, int H, int W, int ss, int width, const float *depth0,
                                      unsigned long long *keys, int32_t *dropped, hipStream_t st) {
-    const size_t nsub = (size_t)H * ss * W * ss;
-    hipLaunchKernelGGL(mh_photo_fill_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, st, keys, nsub);
-    int rc = (int)hipGetLastError();
+    int rc = mh_fill_u32(keys, 0xffffffffu, 2 * ((size_t)H * ss * W * ss), st);      // (the all-ones 64-bit keys)
     if (rc) return rc;
-    if ((rc = mh_cap_fill(dropped, 0u, 1, st))) return rc;
+    if ((rc = mh_fill_u32(dropped, 0u, 1, st))) return rc;
     if (n_points < 2) return 0;
     hipLaunchKernelGGL(mh_photo_front_kernel, dim3((n_points - 1 + 255) / 256), dim3(256), 0, st, vert, valid, offs, S,
                        n_points, shade, H, W, ss, width, depth0, keys, dropped);

@@ -13,19 +13,9 @@
 #include <stdint.h>
 
 #include "mh_device.h"
+#include "mh_strands.h"      // the strand lookup
 
 #define MH_HM_SPAN 2   // cells along x whose queries share one pass over the targets (see mh_strand_match_kernel)
-
-// the strand of element i: the s with offs[s] <= i < offs[s+1] (offs non-decreasing, offs[0] = 0, i < offs[S])
-__device__ __forceinline__ int mh_hm_strand_of(const int64_t *__restrict__ offs, int S, int64_t i) {
-    int lo = 0, hi = S;      // first s in [0, S] with offs[s] > i, minus one
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > i) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ double mh_hm_norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
 
@@ -52,7 +42,7 @@ __global__ __launch_bounds__(256) void mh_strand_resample_kernel(const float *__
                                                                  double step, float *__restrict__ out) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
-    const int s = mh_hm_strand_of(soffs, S, g);
+    const int s = mh_strand_of(soffs, S, g);
     const int64_t a = offs[s];
     const int n = (int)(offs[s + 1] - a);
     const double *Ls = L + a;
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(256) void mh_strand_tangents_kernel(const float *__
                                                                  double *__restrict__ tan, uint8_t *__restrict__ valid) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int s = mh_hm_strand_of(offs, S, i);
+    const int s = mh_strand_of(offs, S, i);
     const int64_t a = offs[s], b = offs[s + 1];
     const int64_t lo = i - 1 > a ? i - 1 : a, hi = i + 1 < b - 1 ? i + 1 : b - 1;
     const double x = (double)pts[3 * hi] - (double)pts[3 * lo], y = (double)pts[3 * hi + 1] - (double)pts[3 * lo + 1],

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void mh_support_accumulate_kernel(
 #pragma unroll
     for (int q = 0; q < MH_SUP_COLS + MH_SUP_MAX_BOUNDS; ++q) c[q] = 0;
     if (i + 1 < n_points) {
-        s = mh_cap_strand_of(offs, S, i);
+        s = mh_strand_of(offs, S, i);
         MhCapSeg sg;
         bool too_long;
         if (mh_cap_segment_in(vert, valid, offs, S, s, i, sg, too_long)) {

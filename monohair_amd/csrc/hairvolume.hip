@@ -17,18 +17,9 @@
 #include <stdint.h>
 
 #include "mh_device.h"
+#include "mh_fill.h"
+#include "mh_strands.h"      // the strand lookup
 #include "mh_volume.h"
-
-// the strand of point i: the s with offs[s] <= i < offs[s+1] (offs non-decreasing, offs[0] = 0); S when i is beyond them
-__device__ __forceinline__ int mh_vol_strand_of(const int64_t *__restrict__ offs, int S, int64_t i) {
-    int lo = 0, hi = S;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > i) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ bool mh_vol_finite3(double x, double y, double z) {
     return fabs(x) < __builtin_inf() && fabs(y) < __builtin_inf() && fabs(z) < __builtin_inf();      // (NaN fails)
@@ -44,7 +35,7 @@ __global__ __launch_bounds__(256) void mh_strand_volume_accum_kernel(const float
                                                                      unsigned long long *__restrict__ counters) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i + 1 >= n_points) return;
-    const int s = mh_vol_strand_of(offs, S, i);
+    const int s = mh_strand_of(offs, S, i);
     if (s >= S || i + 1 >= offs[s + 1]) return;
     const double wax = (double)pts[3 * i] + gr.bust[0], way = (double)pts[3 * i + 1] + gr.bust[1],
                  waz = (double)pts[3 * i + 2] + gr.bust[2];
@@ -127,11 +118,6 @@ __global__ __launch_bounds__(256) void mh_strand_volume_resolve_kernel(const lon
     double x, y, z;
     coh[g] = mh_tensor_axis(xx, yy, zz, xy, xz, yz, trace, x, y, z);      // (mh_volume.h: shared with hairfill.hip)
     o[0] = (float)x, o[1] = (float)y, o[2] = (float)z;
-}
-
-__global__ __launch_bounds__(256) void mh_volume_fill_kernel(int32_t *__restrict__ p, int32_t value, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = value;
 }
 
 // index[(x*Y + y)*Z + z] = g for voxel g; status[0] += voxels outside the grid, status[1] += voxels met a second time
@@ -221,9 +207,7 @@ extern "C" int mh_launch_strand_volume_resolve(const long long *acc, const int32
 
 extern "C" int mh_launch_volume_index(const long long *voxels, int G, int X, int Y, int Z, int32_t *index, int32_t *status,
                                       hipStream_t st) {
-    const size_t nvox = (size_t)X * Y * Z;
-    hipLaunchKernelGGL(mh_volume_fill_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, st, index, -1, nvox);
-    hipError_t e = hipGetLastError();
+    hipError_t e = (hipError_t)mh_fill_u32(index, 0xffffffffu /* -1 */, (size_t)X * Y * Z, st);
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
     if (G < 1) return 0;

@@ -1,5 +1,6 @@
-// mh_capi.h -- what the translation units of the C ABI (capi*.cpp) share: the context, the error helpers and the one grid
-// rule.  Internal (not installed).  Nothing here is part of the exported surface: all of it has hidden visibility.
+// mh_capi.h -- what the translation units of the C ABI (capi*.cpp) share: the context, the error helpers, the one grid
+// rule, the strand tools' checks and scratch front.  Internal (not installed).  Nothing here is part of the exported
+// surface: all of it has hidden visibility.
 // capi_host.cpp, which must build without HIP, does not include this file; it defines fail().
 #pragma once
 #include <cstdint>
@@ -112,5 +113,39 @@ int launched(int rc, const char *what);        // capi.cpp: a launcher's return 
 inline bool cells_fit_int32(int x, int y, int z) {
     return x >= 1 && y >= 1 && z >= 1 && (long long)x * y < (1ll << 31) && (long long)x * y * z < (1ll << 31);
 }
+
+// ---- what the entry points of the strand tools share (capi_capture.cpp, capi_reproj.cpp, capi_volume.cpp)
+#define MH_MAX_RADIUS 16      // the largest splat radius of the capture and of the capture agreement
+
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+// an image of H * W pixels that an int32 can index
+inline bool image_fits_int32(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+
+// a strand set (points or projected vertices, valid, offsets): an empty one needs no pointer, any other needs all of them
+// and a strand.  has_valid = false: the entry point takes no `valid` (mh_strand_volume_accumulate)
+inline bool strands_ok(const float *points, const uint8_t *valid, const long long *offsets, int n_strands, int n_points,
+                       bool has_valid = true) {
+    return n_strands >= 0 && n_points >= 0 && (n_points == 0 || (points && (valid || !has_valid) && offsets && n_strands >= 1));
+}
+
+// The front of every per-view scratch (mh_capture_view, mh_photo_view, mh_support_view): dropped 256 B | vert | valid, then
+// whatever the deriving layout take()s, every region on a 256 B boundary.  The size queries construct a layout on a null
+// base and read `bytes`; the entry points construct the same layout on the caller's buffer.
+struct ViewScratch {
+    int32_t *dropped;
+    float *vert;
+    uint8_t *valid;
+    size_t n, bytes = 0;      // n: the points the per-point regions are sized for (at least 1)
+    ViewScratch(int n_points, void *base) : n((size_t)(n_points > 0 ? n_points : 1)), base_((uintptr_t)base) {
+        dropped = take<int32_t>(256), vert = take<float>(n * 12), valid = take<uint8_t>(n);
+    }
+    template <typename T>
+    T *take(size_t b) {      // the next region, of b bytes
+        bytes += align256(b);
+        return (T *)(base_ + bytes - align256(b));
+    }
+    uintptr_t base_;      // (an integer: the size queries pass no buffer)
+};
 
 #pragma GCC visibility pop

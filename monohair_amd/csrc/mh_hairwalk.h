@@ -6,17 +6,7 @@
 #include <stdint.h>
 
 #include "mh_launch.h"
-
-// the strand of point i: the s with offs[s] <= i < offs[s+1] (offs non-decreasing, offs[0] = 0, i < offs[S])
-__device__ __forceinline__ int mh_cap_strand_of(const int64_t *__restrict__ offs, int S, int64_t i) {
-    int lo = 0, hi = S;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid + 1] > i) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
+#include "mh_strands.h"      // the strand lookup
 
 // What the passes need of segment (i, i+1), the same arithmetic in all of them.
 struct MhCapSeg {
@@ -25,7 +15,7 @@ struct MhCapSeg {
     long long qc, qs;
 };
 
-// true: points i and i+1 are consecutive points of strand s = mh_cap_strand_of(i) and both valid
+// true: points i and i+1 are consecutive points of strand s = mh_strand_of(i) and both valid
 __device__ __forceinline__ bool mh_cap_pair_in(const uint8_t *__restrict__ valid, const int64_t *__restrict__ offs, int S,
                                                int s, int64_t i) {
     return s < S && i + 1 < offs[s + 1] && valid[i] && valid[i + 1];                    // (s = S: i beyond the offsets)
@@ -34,7 +24,7 @@ __device__ __forceinline__ bool mh_cap_pair_in(const uint8_t *__restrict__ valid
 // true: points i and i+1 are consecutive points of one strand and both valid
 __device__ __forceinline__ bool mh_cap_pair(const uint8_t *__restrict__ valid, const int64_t *__restrict__ offs, int S,
                                             int64_t i) {
-    return mh_cap_pair_in(valid, offs, S, mh_cap_strand_of(offs, S, i), i);
+    return mh_cap_pair_in(valid, offs, S, mh_strand_of(offs, S, i), i);
 }
 
 // the walk from (r0, c0, z0) to (r1, c1, z1), in whatever units the caller's grid has: the steps and the sample count.
@@ -51,7 +41,7 @@ __device__ __forceinline__ bool mh_cap_walk(MhCapSeg &sg, double r0, double c0, 
     return true;
 }
 
-// The segment that starts at point i of strand s = mh_cap_strand_of(i).  false: there is none (last point of its strand, an
+// The segment that starts at point i of strand s = mh_strand_of(i).  false: there is none (last point of its strand, an
 // invalid end), or it is dropped (n > MH_CAP_MAXN: *too_long)
 __device__ __forceinline__ bool mh_cap_segment_in(const float *__restrict__ vert, const uint8_t *__restrict__ valid,
                                                   const int64_t *__restrict__ offs, int S, int s, int64_t i, MhCapSeg &sg,
@@ -77,7 +67,7 @@ __device__ __forceinline__ bool mh_cap_segment_in(const float *__restrict__ vert
 __device__ __forceinline__ bool mh_cap_segment(const float *__restrict__ vert, const uint8_t *__restrict__ valid,
                                                const int64_t *__restrict__ offs, int S, int64_t i, MhCapSeg &sg,
                                                bool &too_long) {
-    return mh_cap_segment_in(vert, valid, offs, S, mh_cap_strand_of(offs, S, i), i, sg, too_long);
+    return mh_cap_segment_in(vert, valid, offs, S, mh_strand_of(offs, S, i), i, sg, too_long);
 }
 
 // sample j of a segment: centre pixel and depth; false when the depth is not finite (no fragment)

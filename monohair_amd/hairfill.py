@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import host_ptr
-from .hairvolume import _dims, _load_side
+from .hairvolume import grid_dims3, load_side
 from .pmvo_utils import GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE
 from .timing import stage
 
@@ -33,7 +33,7 @@ def _grid(voxel_min, voxel_size, grid_resolution):
     vs = float(voxel_size)
     if vmin.shape != (3,) or not (np.isfinite(vmin).all() and vs > 0.0 and math.isfinite(vs)):
         raise ValueError("voxel_min is three finite numbers, voxel_size a positive one")
-    return vmin, vs, _dims(grid_resolution)
+    return vmin, vs, grid_dims3(grid_resolution)
 
 
 def _voxel_list(voxels):
@@ -204,7 +204,7 @@ def fill_inner(pmvo, bust, ext_volume, sweeps=64, min_coh=0.0, max_bad=0, voxel_
     diffuse_orientation.  bust: float32 [V,H,W] planes of the bust alone, or (vertices, faces) in world coordinates;
     ext_volume: a directory of Occ3D.mat / Ori3D.mat, or (grid_resolution, voxels, ori).  -> float32 [M,7]; with
     return_details also a dict: diffuse_orientation's, and domain int64 [D,3]."""
-    grid, ev, eo = _load_side(ext_volume)
+    grid, ev, eo = load_side(ext_volume)
     domain = inner_domain(pmvo, bust, ev, grid, voxel_min, voxel_size, max_bad)
     rows, details = diffuse_orientation(ev, eo, domain, grid, sweeps, min_coh, True, voxel_min, voxel_size, pmvo.device)
     if not return_details:

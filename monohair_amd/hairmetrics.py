@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._lib import host_ptr
 from .hairgrow import grid_dims
-from .pmvo_utils import load_strand
+from .strandset import StrandSet
 
 DEFAULT_THRESHOLDS = ((0.001, 10.0), (0.002, 20.0), (0.003, 30.0))   # (metres, degrees)
 MAX_PAIRS = 8                                                        # one bit of the flag byte each
@@ -61,21 +61,9 @@ def _dev(a, dtype, device):
                                                            torch.uint8: np.uint8}[dtype])).to(device)
 
 
-def _strands_dev(counts, points, device):
-    """-> (counts int64 [S] host, offsets int64 [S+1] device, points float32 [n,3] device)"""
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-    pts = _dev(points, torch.float32, device).reshape(-1, 3)
-    if (counts < 0).any() or int(counts.sum()) != pts.shape[0]:
-        raise ValueError("the strand counts sum to %d, there are %d points" % (int(counts.sum()), pts.shape[0]))
-    if pts.shape[0] >= 1 << 31:
-        raise ValueError("more than 2^31 - 1 points")
-    offs = np.zeros(counts.shape[0] + 1, np.int64)
-    np.cumsum(counts, out=offs[1:])
-    return counts, torch.from_numpy(offs).to(device), pts
-
-
-def _resample_dev(counts, offs, pts, step, device):
-    S = counts.shape[0]
+def _resample_dev(s, step, device):
+    """the strand set resampled -> (counts int64 [S] host, offsets int64 [S+1] device, points float32 [m,3] device)"""
+    counts, offs, pts, S = s.counts, s.offsets, s.points, s.S
     step = float(step)
     if not (step > 0.0 and math.isfinite(step)):
         raise ValueError("step must be a positive length, got %r" % step)
@@ -109,7 +97,7 @@ def _tangents_dev(counts, offs, pts, device):
 def resample_strands(counts, points, step, device="cuda:0"):
     """Every strand resampled on its own at arc-length spacing `step` (metres) -> (counts int64 [S], points float32 [m,3])."""
     with torch.cuda.device(device):
-        c, _, p = _resample_dev(*_strands_dev(counts, points, device), step, device)
+        c, _, p = _resample_dev(StrandSet((counts, points), device), step, device)
         return c, p.cpu().numpy()
 
 
@@ -117,8 +105,8 @@ def strand_tangents(counts, points, device="cuda:0"):
     """-> (unit tangents float64 [n,3], valid uint8 [n]): central differences inside a strand, one-sided at its ends; a point
     of a one-point strand, or between coincident neighbours, has no direction (tangent 0, valid 0)."""
     with torch.cuda.device(device):
-        c, o, p = _strands_dev(counts, points, device)
-        tan, valid = _tangents_dev(c, o, p, device)
+        s = StrandSet((counts, points), device)
+        tan, valid = _tangents_dev(s.counts, s.offsets, s.points, device)
         return tan.cpu().numpy(), valid.cpu().numpy()
 
 
@@ -197,7 +185,8 @@ def match_flags(q_pts, q_tan, q_valid, t_pts, t_tan, t_valid, dist=None, angle_d
         return _match_dev(qp, qt, qv, targets, r2, cos, device).cpu().numpy()
 
 
-def _flag_counts(flags, valid, device):
+def flag_counts(flags, valid, device):
+    """the nine numbers of mh_flag_counts as ints: per bit k < 8 the flag bytes that have it, then the non-zero bytes of `valid`"""
     out = torch.empty(9, dtype=torch.int64, device=device)
     _lib.check(_lib.lib().mh_flag_counts(_lib.bare_ctx(device), _lib.ptr(flags), _lib.ptr(valid), int(flags.shape[0]),
                                          _lib.ptr(out), _lib.stream_ptr()), "mh_flag_counts")
@@ -223,13 +212,6 @@ def build_result(thresholds, step, counts, points, strands):
             "precision": P, "recall": R, "f_score": F, "counts": counts, "points": points, "strands": strands}
 
 
-def _load(x):
-    if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
-        counts, points = load_strand(x)
-        return counts, points.astype(np.float32)      # (load_strand widens the file's float32: exact both ways)
-    return x
-
-
 def score_strands(pred, gt, thresholds=DEFAULT_THRESHOLDS, step=None, device="cuda:0", return_flags=False):
     """Precision (predicted points that have a ground-truth point within the bounds), recall (the roles swapped) and F-score
     per threshold pair (metres, degrees).  pred / gt: a `.hair` path or (counts, points).  step: resample both sets at this
@@ -242,9 +224,8 @@ def score_strands(pred, gt, thresholds=DEFAULT_THRESHOLDS, step=None, device="cu
     sides = {}
     with torch.cuda.device(device):
         for name, src in (("pred", pred), ("gt", gt)):
-            c, o, p = _strands_dev(*_load(src), device)
-            if step is not None:
-                c, o, p = _resample_dev(c, o, p, step, device)
+            s = StrandSet(src, device)
+            c, o, p = (s.counts, s.offsets, s.points) if step is None else _resample_dev(s, step, device)
             tan, valid = _tangents_dev(c, o, p, device)
             sides[name] = (c, p, tan, valid)
         flags = {}
@@ -254,7 +235,7 @@ def score_strands(pred, gt, thresholds=DEFAULT_THRESHOLDS, step=None, device="cu
             flags[name] = _match_dev(p, tan, valid, _Targets(op, otan, ovalid, reach, device), r2, cos, device)
         counts = {}
         for name in ("pred", "gt"):
-            c = _flag_counts(flags[name], sides[name][3], device)
+            c = flag_counts(flags[name], sides[name][3], device)
             n = int(sides[name][1].shape[0])
             counts[name] = {"matched": c[:K], "valid": c[8], "invalid": n - c[8]}
     result = build_result(thresholds, step, counts, {name: int(sides[name][1].shape[0]) for name in sides},

@@ -22,8 +22,8 @@ import torch
 
 from . import _lib
 from ._lib import host_ptr
-from .camera import camera_records
-from .pmvo_utils import load_strand, map_code_lut, save_hair_strands, write_strand
+from .pmvo_utils import map_code_lut, save_hair_strands, write_strand
+from .strandset import Occluder, StrandSet, load, records
 from .synth_hair import code_table
 
 COLS = 4                     # visible, on hair, confident, dropped segments; then one column per angle
@@ -45,24 +45,6 @@ def angle_bounds(angles_deg):
     if not 1 <= len(angles) <= MAX_ANGLES or not all(0.0 <= a <= 90.0 for a in angles):
         raise ValueError("between 1 and %d angles within [0, 90] degrees" % MAX_ANGLES)
     return angles, np.array([4096.0 * math.cos(2.0 * (a * (math.pi / 180.0))) for a in angles], np.float64)
-
-
-def _load(x):
-    if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
-        counts, points = load_strand(x)
-        return np.asarray(counts, np.int64), points.astype(np.float32)      # (load_strand widens the file's float32)
-    return x
-
-
-def _strands(strands):
-    counts, points = _load(strands)
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-    points = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
-    if (counts < 0).any() or int(counts.sum()) != points.shape[0]:
-        raise ValueError("the strand counts sum to %d, there are %d points" % (int(counts.sum()), points.shape[0]))
-    if points.shape[0] >= 1 << 31:
-        raise ValueError("more than 2^31 - 1 points")
-    return counts, points
 
 
 def _plane(a, device):
@@ -93,13 +75,9 @@ def support_counts(strands, camera, planes, bust=None, bust_to_origin=(0.0, 0.0,
         raise _lib.MhError("monohair_amd.hairreproj needs a ROCm GPU: the scorer has no CPU fallback")
     device = torch.device(device)
     radius = int(radius)
-    counts, pts_h = _strands(strands)
-    b = np.asarray(bust_to_origin, np.float64).reshape(3)
-    pts_h = np.ascontiguousarray((pts_h.astype(np.float64) + b).astype(np.float32))
-    S, n = int(counts.shape[0]), int(pts_h.shape[0])
-    offs_h = np.zeros(S + 1, np.int64)
-    np.cumsum(counts, out=offs_h[1:])
-    recs = np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
+    s = StrandSet(strands, device, shift=bust_to_origin)
+    S, n, pts, offs = s.S, s.n, s.points, s.offsets
+    recs = records(camera)
     V = recs.shape[0]
     _, bounds = angle_bounds(angles_deg)
     K = int(bounds.shape[0])
@@ -115,19 +93,13 @@ def support_counts(strands, camera, planes, bust=None, bust_to_origin=(0.0, 0.0,
         need = int(L.mh_support_scratch_bytes(n, H, W))
         if need == 0:
             raise ValueError("support_counts: H * W < 2^31")
-        pts = torch.from_numpy(pts_h).to(device)
-        offs = torch.from_numpy(offs_h).to(device)
         scratch = torch.empty(need, dtype=torch.uint8, device=device)
         strand = torch.zeros((max(S, 1), COLS + K), dtype=torch.int64, device=device)
         view = torch.zeros((V, COLS + K), dtype=torch.int64, device=device)
         sil = torch.zeros((V, 3), dtype=torch.int64, device=device)
         details = torch.zeros((V, max(S, 1), COLS + K), dtype=torch.int64, device=device) if return_details else None
-        renderer = None
-        if bust is not None:
-            from .render import DepthRenderer
-
-            renderer = DepthRenderer([bust], device)
-        depth0 = [renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None for v in range(V)]
+        occluder = Occluder(bust, device)
+        depth0 = [occluder.plane(recs[v], H, W, pixel_center) for v in range(V)]
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         for v in range(V):
@@ -181,7 +153,7 @@ def score_support(strands, camera, planes, bust=None, bust_to_origin=(0.0, 0.0, 
                   conf_threshold=0.15, radius=1, tol=0.25, device="cuda:0", return_counts=False, timing=None):
     """support_counts and the ratios made of it -> dict (build_result); with return_counts also the per-strand rows."""
     angles, _ = angle_bounds(angles_deg)
-    counts, points = _strands(strands)
+    counts, points = load(strands)
     sc, vc, sil = support_counts((counts, points), camera, planes, bust, bust_to_origin, angles, conf_threshold, radius, tol,
                                  device, timing=timing)
     result = build_result(angles, conf_threshold, radius, tol, sc, vc, sil, points.shape[0])
@@ -204,7 +176,7 @@ def prune_strands(strands, counts, min_cover=0.5, min_agree=0.5, angle_index=-1,
     min_visible visible samples was not seen: it is kept unless drop_unseen is set.  A strand that was seen is kept iff
     on_hair >= min_cover * visible and agrees[angle_index] >= min_agree * confident (float64 products, both bounds included).
     -> ((counts, points) of the kept strands, the boolean mask [S]).  The default thresholds are inputs, not claims."""
-    n_pts, points = _strands(strands)
+    n_pts, points = load(strands)
     rows = np.asarray(counts, np.int64)
     if rows.ndim != 2 or rows.shape[0] != n_pts.shape[0] or rows.shape[1] <= COLS:
         raise ValueError("one counter row of at least %d columns per strand" % (COLS + 1))

@@ -22,9 +22,10 @@ import torch
 
 from . import _lib
 from ._lib import host_ptr
-from .hairmetrics import _flag_counts, scores_from_counts
+from .hairmetrics import flag_counts, scores_from_counts
 from .pmvo_utils import (GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE, get_ground_truth_3D_occ, get_ground_truth_3D_ori,
-                         load_strand, save_ori_occ_mat_sparse)
+                         save_ori_occ_mat_sparse)
+from .strandset import StrandSet, load
 
 DEFAULT_THRESHOLDS = ((0, None), (1, None), (1, 30.0), (1, 20.0), (1, 10.0))   # (reach in voxels, degrees or None)
 MAX_PAIRS = 8          # one bit of the flag byte each
@@ -32,18 +33,12 @@ MAX_REACH = 4
 MAX_COUNT = 1 << 29    # samples of one voxel: up to here its six sums convert to float64 exactly
 
 
-def _dims(grid_resolution):
+def grid_dims3(grid_resolution):
+    """int32 [3] = (X, Y, Z): three positive sizes with fewer than 2^31 voxels"""
     g = np.ascontiguousarray(np.asarray(grid_resolution).reshape(-1), dtype=np.int64)
     if g.shape != (3,) or (g < 1).any() or int(np.prod(g)) >= 1 << 31:
         raise ValueError("grid_resolution %r: three positive sizes with fewer than 2^31 voxels" % (grid_resolution,))
     return g.astype(np.int32)
-
-
-def _load_strands(x):
-    if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
-        counts, points = load_strand(x)
-        return counts, points.astype(np.float32)      # (load_strand widens the file's float32: exact both ways)
-    return x
 
 
 # ------------------------------------------------------------------------------------------------- strands -> volume
@@ -53,13 +48,7 @@ def voxelize_strands(strands, bust_to_origin=(0.0, 0.0, 0.0), voxel_min=VOXEL_MI
     voxels int64 [G,3] (x,y,z) ascending by (x*Y + y)*Z + z, ori float32 [G,3] (world directions, y <= 0), cnt int32 [G],
     coh float64 [G], dropped_segments, outside_samples, samples (the kept ones), grid_resolution; with return_details also
     sums int64 [G,6] (xx, yy, zz, xy, xz, yz of the quantised directions)."""
-    counts, points = _load_strands(strands)
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
-    if (counts < 0).any() or int(counts.sum()) != pts.shape[0]:
-        raise ValueError("the strand counts sum to %d, there are %d points" % (int(counts.sum()), pts.shape[0]))
-    if pts.shape[0] >= 1 << 31:
-        raise ValueError("more than 2^31 - 1 points")
+    strands = load(strands)
     sub = int(sub)
     if not 1 <= sub <= 16:
         raise ValueError("sub must be 1..16, got %r" % sub)
@@ -69,20 +58,17 @@ def voxelize_strands(strands, bust_to_origin=(0.0, 0.0, 0.0), voxel_min=VOXEL_MI
     if bust.shape != (3,) or vmin.shape != (3,) or not (np.isfinite(bust).all() and np.isfinite(vmin).all()
                                                          and vs > 0.0 and math.isfinite(vs)):
         raise ValueError("bust_to_origin and voxel_min are three finite numbers, voxel_size a positive one")
-    dims = _dims(grid_resolution)
+    dims = grid_dims3(grid_resolution)
     nvox = int(np.prod(dims.astype(np.int64)))
-    S, n = int(counts.shape[0]), int(pts.shape[0])
-    offs = np.zeros(S + 1, np.int64)
-    np.cumsum(counts, out=offs[1:])
     L = _lib.lib()
     with torch.cuda.device(device):
         ctx, st = _lib.bare_ctx(device), _lib.stream_ptr()
-        pd = torch.from_numpy(pts).to(device)
-        od = torch.from_numpy(offs).to(device)
+        s = StrandSet(strands, device)
+        S = s.S
         acc = torch.empty((nvox, 8), dtype=torch.int64, device=device)
         occ = torch.empty(nvox, dtype=torch.uint8, device=device)
         counters = torch.empty(2, dtype=torch.int64, device=device)
-        _lib.check(L.mh_strand_volume_accumulate(ctx, _lib.ptr(pd), _lib.ptr(od), S, n, host_ptr(bust), host_ptr(vmin), vs,
+        _lib.check(L.mh_strand_volume_accumulate(ctx, _lib.ptr(s.points), _lib.ptr(s.offsets), S, s.n, host_ptr(bust), host_ptr(vmin), vs,
                                                  host_ptr(dims), sub, _lib.ptr(acc), _lib.ptr(occ), _lib.ptr(counters), st),
                    "mh_strand_volume_accumulate")
         index = torch.empty(nvox, dtype=torch.int32, device=device)
@@ -115,7 +101,7 @@ def voxelize_strands(strands, bust_to_origin=(0.0, 0.0, 0.0), voxel_min=VOXEL_MI
 def write_volume(dir, grid_resolution, voxels, ori):
     """Occ3D.mat / Ori3D.mat under `dir`, byte for byte the layout PMVO writes (save_ori_occ_mat_sparse)."""
     os.makedirs(dir, exist_ok=True)
-    save_ori_occ_mat_sparse(dir, _dims(grid_resolution), voxels, ori)
+    save_ori_occ_mat_sparse(dir, grid_dims3(grid_resolution), voxels, ori)
 
 
 def load_volume(dir):
@@ -208,13 +194,13 @@ def match_volume_flags(q_voxels, q_ori, t_voxels, t_ori, grid_resolution, reach,
     direction b passes cos2[k] < 0 or (a.b)^2 >= cos2[k] * (|a|^2 |b|^2) with |a|^2, |b|^2 > 0 (float64, bound included).
     cos2 is handed to the kernel as it is."""
     reach, cos2 = _bounds(reach, cos2)
-    dims = _dims(grid_resolution)
+    dims = grid_dims3(grid_resolution)
     with torch.cuda.device(device):
         q, t = _Volume(q_voxels, q_ori, dims, device), _Volume(t_voxels, t_ori, dims, device)
         return _match_dev(q, t, dims, reach, cos2, device).cpu().numpy()
 
 
-def _load_side(x):
+def load_side(x):
     """a directory of Occ3D.mat / Ori3D.mat, or (grid_resolution, voxels, ori)"""
     if isinstance(x, (str, bytes)) or hasattr(x, "__fspath__"):
         return load_volume(x)
@@ -237,16 +223,16 @@ def score_volumes(pred, gt, thresholds=DEFAULT_THRESHOLDS, device="cuda:0", retu
     thresholds = _check_thresholds(thresholds)
     K = len(thresholds)
     reach, cos2 = threshold_bounds(thresholds)
-    (gp, vp, op), (gg, vg, og) = _load_side(pred), _load_side(gt)
-    dims = _dims(gp)
-    if [int(v) for v in dims] != [int(v) for v in _dims(gg)]:
+    (gp, vp, op), (gg, vg, og) = load_side(pred), load_side(gt)
+    dims = grid_dims3(gp)
+    if [int(v) for v in dims] != [int(v) for v in grid_dims3(gg)]:
         raise ValueError("the volumes are on different grids: %r and %r" % (list(gp), list(gg)))
     with torch.cuda.device(device):
         sides = {"pred": _Volume(vp, op, dims, device), "gt": _Volume(vg, og, dims, device)}
         flags, counts = {}, {}
         for name, other in (("pred", "gt"), ("gt", "pred")):
             flags[name] = _match_dev(sides[name], sides[other], dims, reach, cos2, device)
-            c = _flag_counts(flags[name], torch.ones_like(flags[name]), device)
+            c = flag_counts(flags[name], torch.ones_like(flags[name]), device)
             counts[name] = {"matched": c[:K], "voxels": c[8]}
     result = build_result(thresholds, counts, dims)
     if return_flags:

@@ -29,8 +29,9 @@ import torch
 
 from . import _lib, synth
 from ._lib import host_ptr
-from .camera import camera_records, cameras_from_list
+from .camera import cameras_from_list
 from .pmvo_utils import load_strand, read_obj, write_strand
+from .strandset import Occluder, StrandSet, load, records
 
 HEAD_R = 0.10          # the scalp sphere of synth.write_case (scalp_tsfm.obj)
 BUST_R = 0.09          # its bust sphere (bust_long_tsfm.obj)
@@ -102,17 +103,26 @@ def make_hairstyle(n_strands=2000, n_points=64, seed=0, length=(0.10, 0.22), gra
     return np.full(n_strands, n_points, np.int64), pts.reshape(-1, 3).astype(np.float32)
 
 
-def _strands(strands):
-    counts, points = strands
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-    points = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
-    if (counts < 0).any() or int(counts.sum()) != points.shape[0]:
-        raise ValueError("the strand counts sum to %d, there are %d points" % (int(counts.sum()), points.shape[0]))
-    if points.shape[0] >= 1 << 31:
-        raise ValueError("more than 2^31 - 1 points")
-    offs = np.zeros(counts.shape[0] + 1, np.int64)
-    np.cumsum(counts, out=offs[1:])
-    return counts, offs, points
+def _empty(device, **specs):
+    """name=(shape, dtype) -> dict of fresh device tensors: the pieces of a view that return_details hands back"""
+    return {k: torch.empty(shape, dtype=dtype, device=device) for k, (shape, dtype) in specs.items()}
+
+
+def _capture_stages(L, ctx, st, s, rec, H, W, radius, tol, n_full, d0, table, out):
+    """One view by the stage calls mh_capture_view makes, on fresh tensors -> the details dict of capture_planes"""
+    p, n = _lib.ptr, s.n
+    b = _empty(s.points.device, vert=((max(n, 1), 3), torch.float32), valid=(max(n, 1), torch.uint8),
+               zmin=((H, W), torch.float32), cnt=((H, W), torch.int32), c2=((H, W), torch.int64), s2=((H, W), torch.int64),
+               dropped=(1, torch.int32))
+    strands = (p(b["vert"]), p(b["valid"]), p(s.offsets), s.S, n, H, W, radius)
+    _lib.check(L.mh_capture_project(ctx, host_ptr(rec), p(s.points), n, H, W, p(b["vert"]), p(b["valid"]), st),
+               "mh_capture_project")
+    _lib.check(L.mh_capture_zmin(ctx, *strands, p(d0), p(b["zmin"]), p(b["dropped"]), st), "mh_capture_zmin")
+    _lib.check(L.mh_capture_accumulate(ctx, *strands, float(tol), p(d0), p(b["zmin"]), p(b["cnt"]), p(b["c2"]), p(b["s2"]), st),
+               "mh_capture_accumulate")
+    _lib.check(L.mh_capture_resolve(ctx, p(b["zmin"]), p(b["cnt"]), p(b["c2"]), p(b["s2"]), p(d0), host_ptr(table), n_full, H,
+                                    W, *out, st), "mh_capture_resolve")
+    return dict(b, vert=b["vert"][:n], valid=b["valid"][:n], dropped=int(b["dropped"].item()), depth0=d0)
 
 
 def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device="cuda:0", return_details=False,
@@ -126,53 +136,28 @@ def capture_planes(strands, camera, H, W, radius=1, tol=0.25, bust=None, device=
     device = torch.device(device)
     H, W, radius = int(H), int(W), int(radius)
     n_full = 2 * radius + 1 if n_full is None else int(n_full)
-    counts, offs_h, pts_h = _strands(strands)
-    S, n = int(counts.shape[0]), int(pts_h.shape[0])
-    recs = np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
+    s = StrandSet(strands, device)
+    recs = records(camera)
     V = recs.shape[0]
     table = code_table()
     L, ctx = _lib.lib(), _lib.bare_ctx(device)
     with torch.cuda.device(device):
         st = _lib.stream_ptr()
-        pts = torch.from_numpy(pts_h).to(device)
-        offs = torch.from_numpy(offs_h).to(device)
         depth = torch.empty((V, H, W), dtype=torch.float32, device=device)
         ori, conf, mask = (torch.empty((V, H, W), dtype=torch.uint8, device=device) for _ in range(3))
-        renderer = None
-        if bust is not None:
-            from .render import DepthRenderer
-
-            renderer = DepthRenderer([bust], device)
+        occluder = Occluder(bust, device)
         details = []
-        scratch = None
-        if not return_details:
-            need = int(L.mh_capture_scratch_bytes(n, H, W))
-            scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        scratch = None if return_details else torch.empty(int(L.mh_capture_scratch_bytes(s.n, H, W)), dtype=torch.uint8,
+                                                          device=device)
         for v in range(V):
-            d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
+            d0 = occluder.plane(recs[v], H, W, pixel_center)
             out = (_lib.ptr(depth[v]), _lib.ptr(ori[v]), _lib.ptr(conf[v]), _lib.ptr(mask[v]))
-            if not return_details:
-                _lib.check(L.mh_capture_view(ctx, host_ptr(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, H, W, radius, float(tol),
-                                             n_full, _lib.ptr(d0), host_ptr(table), _lib.ptr(scratch), scratch.numel(), *out, st),
-                           "mh_capture_view")
+            if return_details:
+                details.append(_capture_stages(L, ctx, st, s, recs[v], H, W, radius, tol, n_full, d0, table, out))
                 continue
-            vert = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
-            valid = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
-            zmin = torch.empty((H, W), dtype=torch.float32, device=device)
-            cnt = torch.empty((H, W), dtype=torch.int32, device=device)
-            c2, s2 = (torch.empty((H, W), dtype=torch.int64, device=device) for _ in range(2))
-            dropped = torch.empty(1, dtype=torch.int32, device=device)
-            _lib.check(L.mh_capture_project(ctx, host_ptr(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
-                       "mh_capture_project")
-            _lib.check(L.mh_capture_zmin(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, H, W, radius,
-                                         _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(dropped), st), "mh_capture_zmin")
-            _lib.check(L.mh_capture_accumulate(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, H, W, radius,
-                                               float(tol), _lib.ptr(d0), _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2),
-                                               _lib.ptr(s2), st), "mh_capture_accumulate")
-            _lib.check(L.mh_capture_resolve(ctx, _lib.ptr(zmin), _lib.ptr(cnt), _lib.ptr(c2), _lib.ptr(s2), _lib.ptr(d0),
-                                            host_ptr(table), n_full, H, W, *out, st), "mh_capture_resolve")
-            details.append(dict(vert=vert[:n], valid=valid[:n], zmin=zmin, cnt=cnt, c2=c2, s2=s2, dropped=int(dropped.item()),
-                                depth0=d0))
+            _lib.check(L.mh_capture_view(ctx, host_ptr(recs[v]), _lib.ptr(s.points), _lib.ptr(s.offsets), s.S, s.n, H, W, radius,
+                                         float(tol), n_full, _lib.ptr(d0), host_ptr(table), _lib.ptr(scratch), scratch.numel(),
+                                         *out, st), "mh_capture_view")
         torch.cuda.current_stream().synchronize()      # (the occluder plane and the scratch are read asynchronously)
     if return_details:
         return depth, ori, conf, mask, details
@@ -187,15 +172,28 @@ def strand_albedo(n_strands, seed=0, lo=PHOTO_ALBEDO[0], hi=PHOTO_ALBEDO[1]):
     return np.random.default_rng([int(seed), 1]).uniform(float(lo), float(hi), int(n_strands)).astype(np.float32)
 
 
-def _records(camera):
-    return np.ascontiguousarray(camera_records(camera) if isinstance(camera, dict) else camera, dtype=np.float32)
-
-
 def light_directions(camera):
     """float64 [V,3], unit length: per view the world direction towards the camera -- the third row of the rotation of its
     world-to-camera pose (the camera looks down -z), normalised -- a head light."""
-    r = _records(camera)[:, 8:11].astype(np.float64)
+    r = records(camera)[:, 8:11].astype(np.float64)
     return r / np.sqrt((r * r).sum(1))[:, None]
+
+
+def _photo_stages(L, ctx, st, s, rec, shading, H, W, ss, width, d0, bust_code, background_code, gray):
+    """One view by the stage calls mh_photo_view makes, on fresh tensors -> the details dict of photo_planes"""
+    p, n = _lib.ptr, s.n
+    b = _empty(s.points.device, vert=((max(n, 1), 3), torch.float32), valid=(max(n, 1), torch.uint8),
+               shade=(max(n, 1), torch.uint8), keys=((ss * H, ss * W), torch.int64), cover=((H, W), torch.int32),
+               dropped=(1, torch.int32))
+    _lib.check(L.mh_capture_project(ctx, host_ptr(rec), p(s.points), n, H, W, p(b["vert"]), p(b["valid"]), st),
+               "mh_capture_project")
+    _lib.check(L.mh_photo_shade(ctx, p(s.points), p(b["valid"]), p(s.offsets), s.S, n, *shading, p(b["shade"]), st),
+               "mh_photo_shade")
+    _lib.check(L.mh_photo_front(ctx, p(b["vert"]), p(b["valid"]), p(s.offsets), s.S, n, p(b["shade"]), H, W, ss, width, p(d0),
+                                p(b["keys"]), p(b["dropped"]), st), "mh_photo_front")
+    _lib.check(L.mh_photo_resolve(ctx, p(b["keys"]), p(d0), H, W, ss, bust_code, background_code, gray, p(b["cover"]), st),
+               "mh_photo_resolve")
+    return dict(b, vert=b["vert"][:n], valid=b["valid"][:n], shade=b["shade"][:n], dropped=int(b["dropped"].item()), depth0=d0)
 
 
 def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHOTO_WIDTH, ambient=PHOTO_AMBIENT, albedo=None,
@@ -211,9 +209,9 @@ def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHO
         raise _lib.MhError("monohair_amd.synth_hair needs a ROCm GPU: the renderer has no CPU fallback")
     device = torch.device(device)
     H, W, ss, width = int(H), int(W), int(supersample), int(width)
-    counts, offs_h, pts_h = _strands(strands)
-    S, n = int(counts.shape[0]), int(pts_h.shape[0])
-    recs = _records(camera)
+    s = StrandSet(strands, device)
+    S, n = s.S, s.n
+    recs = records(camera)
     V = recs.shape[0]
     albedo_h = strand_albedo(S, seed) if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(-1)
     if albedo_h.shape[0] != S or not (np.isfinite(albedo_h).all() and (albedo_h >= 0).all()):
@@ -227,41 +225,21 @@ def photo_planes(strands, camera, H, W, supersample=PHOTO_SUPERSAMPLE, width=PHO
         raise ValueError("photo_planes: supersample in {1, 2, 4, 8} and supersample^2 * H * W < 2^31")
     with torch.cuda.device(device):
         st = _lib.stream_ptr()
-        pts = torch.from_numpy(pts_h).to(device)
-        offs = torch.from_numpy(offs_h).to(device)
         alb = torch.from_numpy(albedo_h if S else np.zeros(1, np.float32)).to(device)
         gray = torch.empty((V, H, W), dtype=torch.uint8, device=device)
-        renderer = None
-        if bust is not None:
-            from .render import DepthRenderer
-
-            renderer = DepthRenderer([bust], device)
+        occluder = Occluder(bust, device)
         details = []
         scratch = None if return_details else torch.empty(need, dtype=torch.uint8, device=device)
         for v in range(V):
-            d0 = renderer.render(recs[v], H, W, pixel_center) if renderer is not None else None
-            if not return_details:
-                _lib.check(L.mh_photo_view(ctx, host_ptr(recs[v]), _lib.ptr(pts), _lib.ptr(offs), S, n, _lib.ptr(alb),
-                                           host_ptr(light_h[v]), float(ambient), H, W, ss, width, _lib.ptr(d0), int(bust_code),
-                                           int(background_code), _lib.ptr(scratch), scratch.numel(), _lib.ptr(gray[v]), None,
-                                           st), "mh_photo_view")
+            d0 = occluder.plane(recs[v], H, W, pixel_center)
+            shading = (_lib.ptr(alb), host_ptr(light_h[v]), float(ambient))
+            if return_details:
+                details.append(_photo_stages(L, ctx, st, s, recs[v], shading, H, W, ss, width, d0, int(bust_code),
+                                             int(background_code), _lib.ptr(gray[v])))
                 continue
-            vert = torch.empty((max(n, 1), 3), dtype=torch.float32, device=device)
-            valid = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
-            shade = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
-            keys = torch.empty((ss * H, ss * W), dtype=torch.int64, device=device)
-            cover = torch.empty((H, W), dtype=torch.int32, device=device)
-            dropped = torch.empty(1, dtype=torch.int32, device=device)
-            _lib.check(L.mh_capture_project(ctx, host_ptr(recs[v]), _lib.ptr(pts), n, H, W, _lib.ptr(vert), _lib.ptr(valid), st),
-                       "mh_capture_project")
-            _lib.check(L.mh_photo_shade(ctx, _lib.ptr(pts), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(alb),
-                                        host_ptr(light_h[v]), float(ambient), _lib.ptr(shade), st), "mh_photo_shade")
-            _lib.check(L.mh_photo_front(ctx, _lib.ptr(vert), _lib.ptr(valid), _lib.ptr(offs), S, n, _lib.ptr(shade), H, W, ss,
-                                        width, _lib.ptr(d0), _lib.ptr(keys), _lib.ptr(dropped), st), "mh_photo_front")
-            _lib.check(L.mh_photo_resolve(ctx, _lib.ptr(keys), _lib.ptr(d0), H, W, ss, int(bust_code), int(background_code),
-                                          _lib.ptr(gray[v]), _lib.ptr(cover), st), "mh_photo_resolve")
-            details.append(dict(vert=vert[:n], valid=valid[:n], shade=shade[:n], keys=keys, cover=cover,
-                                dropped=int(dropped.item()), depth0=d0))
+            _lib.check(L.mh_photo_view(ctx, host_ptr(recs[v]), _lib.ptr(s.points), _lib.ptr(s.offsets), S, n, *shading, H, W,
+                                       ss, width, _lib.ptr(d0), int(bust_code), int(background_code), _lib.ptr(scratch),
+                                       scratch.numel(), _lib.ptr(gray[v]), None, st), "mh_photo_view")
         torch.cuda.current_stream().synchronize()      # (the occluder plane and the scratch are read asynchronously)
     if return_details:
         return gray, details
@@ -273,7 +251,7 @@ def write_geometry(base, strands, cams, seed=0):
     spheres of synth.write_case (the scalp with `vn` records), ours/colmap_points.obj -- a vertices-only OBJ of the strand
     points (a seeded subsample beyond MAX_COLMAP_POINTS), which the candidate sampling of PMVO.py reads -- and
     gt_strands.hair, the ground truth.  -> (counts, points) as written"""
-    counts, _, points = _strands(strands)
+    counts, points = load(strands)
     if counts.size and counts.max() >= 65536:
         raise ValueError("a strand of %d points: a .hair file counts them in 16 bits" % int(counts.max()))
     os.makedirs(os.path.join(base, "ours"), exist_ok=True)

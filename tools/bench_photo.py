@@ -14,7 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from monohair_amd import _lib, synth, synth_hair as sh          # noqa: E402
+from monohair_amd import _lib, strandset, synth, synth_hair as sh          # noqa: E402
 from monohair_amd.camera import camera_records, cameras_from_list          # noqa: E402
 from monohair_amd.pmvo_utils import _ctx_for          # noqa: E402
 
@@ -33,8 +33,7 @@ def main():
     counts, points = sh.make_hairstyle(args.strands, 64, seed=0)
     recs = camera_records(cameras_from_list(synth.make_cameras(V, H, W)))
     light = sh.light_directions(recs)
-    offs_h = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(counts, out=offs_h[1:])
+    offs_h = strandset.offsets(counts)
     n, S = len(points), len(counts)
     L, ctx, st, p = _lib.lib(), _ctx_for(dev), _lib.stream_ptr(), _lib.ptr
     pts, offs = torch.from_numpy(points).to(dev), torch.from_numpy(offs_h).to(dev)
