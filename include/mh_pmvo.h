@@ -793,6 +793,61 @@ int mh_inner_resolve(mh_ctx *ctx, const long long *dom_voxels, int n_dom, const 
                      const double *voxel_min, double voxel_size, const int32_t *dims, double min_coh, float *world, float *ori,
                      double *coh, uint8_t *emit, void *stream);
 
+/* Silhouette carve (monohair_amd.haircarve; no counterpart in the reference, whose coarse surface `ours/colmap_points.obj` and
+ * depth maps `render_depth/` come from instant-ngp): the visual hull of the hair masks outside the head, as vote counts, as
+ * flags and as a closed triangle mesh.  The conventions are those of "Inner fill": voxel_min [3] and voxel_size are HOST
+ * float64 (finite, voxel_size > 0), dims = (X, Y, Z) HOST int32 with X*Y*Z < 2^31; the votes compare float32 values as the vote
+ * kernels do; positions are float64 arithmetic rounded once to float32, nothing fused.  The rule has two parts.
+ *
+ * 1. Votes, for the centre of every voxel (x, y, z) of the grid: the float32 world point w of "Inner fill" part 1 (the same
+ *   device function, csrc/mh_volume.h).  For every view of the context (fp32 planes or 8-bit codes) w is projected, its pixel p
+ *   rounded and clamped, and z' and z255 formed exactly as there, and the view ABSTAINS exactly as there: the pixel is out of
+ *   the image, or not z' > 0 (a NaN point abstains everywhere).  Otherwise
+ *     free = z255 <= bust[p]                       bust: float32 [V,H,W], the depth plane of the bust ALONE, 255 where there is
+ *                                                  none: the bust's front face does not hide the voxel; equality counts as free
+ *     hair = mask[p] > 0.2                         as the votes read the mask
+ *   and the voxel's three int32 counts are n_in (views that do not abstain), n_free (free) and n_miss (free and not hair): on
+ *   any context the columns n_in, n_front and n_bad of mh_inner_votes.  Only the cameras and the mask planes of the context are
+ *   read (never depth, orientation or confidence).  The voxel is INSIDE iff n_free >= min_free and n_miss <= max_miss (HOST
+ *   ints, min_free >= 1, max_miss >= 0; the defaults of the Python layer are 2 and 0).  A voxel that the bust hides in every
+ *   view is inside the head: n_free = 0, never INSIDE.
+ * 2. The hull as a mesh, of uint8 flags [X*Y*Z] (non-zero = INSIDE) at (x*Y + y)*Z + z, whatever made them.  Walk the INSIDE
+ *   voxels ascending by (x*Y + y)*Z + z and, for each, the six directions in the order -x, +x, -y, +y, -z, +z.  A face is
+ *   EXPOSED iff the neighbour in that direction lies outside the grid or is not INSIDE.  Voxel (x, y, z) has the eight grid
+ *   corners (x + di, y + dj, z + dk), di, dj, dk in {0, 1}; the four corners c0..c3 of a face, as (di dj dk):
+ *     -x: 000 001 011 010      +x: 100 110 111 101
+ *     -y: 000 100 101 001      +y: 010 011 111 110
+ *     -z: 000 010 110 100      +z: 001 101 111 011
+ *   Each exposed face gives the triangles (c0, c1, c2) and (c0, c2, c3), in that order.  In voxel coordinates every face is
+ *   counter-clockwise seen from outside (right-handed normal = the direction); world y and z are the negated voxel axes, a
+ *   rotation by half a turn about x, so the same holds in world coordinates: the signed volume of the mesh is the number of
+ *   INSIDE voxels times voxel_size^3.  The VERTICES are the distinct grid corners (i, j, k), 0 <= i <= X, 0 <= j <= Y, 0 <= k <=
+ *   Z, that some exposed face uses, ascending by (i*(Y+1) + j)*(Z+1) + k; corner (i, j, k) lies at
+ *     (vmin.x + (i - 0.5)*vs, -(vmin.y + (j - 0.5)*vs), -(vmin.z + (k - 0.5)*vs))
+ *   in float64 ((i - 0.5) is exact, then one product, one sum, the negation), each component rounded once to float32: a voxel's
+ *   cell is centred on its centre of part 1.  Faces index the vertices from 0 as int32; (X+1)*(Y+1)*(Z+1) < 2^31 is required
+ *   and refused otherwise.  The output order is fixed by this rule: every position is a count of what precedes it (counting
+ *   passes and scans, no atomics).
+ *
+ * mh_carve_votes: bust [V,H,W] float32 on the device, the views of ctx -> counts [X*Y*Z][3] int32 = {n_in, n_free, n_miss}.
+ * mh_carve_inside: -> flags [X*Y*Z] uint8, the decision of part 1.  A voxel leaves its view loop once n_miss > max_miss (the
+ *   decision is then taken: n_miss only grows).
+ * mh_carve_mesh_scratch_bytes: the bytes of `scratch` for these dims (host), 0 for dims that are refused.
+ * mh_carve_mesh_count: flags -> counts (device int64 [2]) = {n_vertices, n_triangles}.
+ * mh_carve_mesh: -> vertices [n_vertices,3] float32, faces [n_triangles,3] int32, for the counts of mh_carve_mesh_count on the
+ *   same flags (HOST values).  It repeats the counting passes, so the scratch carries nothing from call to call; a row at or
+ *   beyond the stated sizes is not written.  Nothing but the two outputs and `scratch` is written. */
+int mh_carve_votes(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                   int32_t *counts, void *stream);
+int mh_carve_inside(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                    int min_free, int max_miss, uint8_t *flags, void *stream);
+size_t mh_carve_mesh_scratch_bytes(const int32_t *dims);
+int mh_carve_mesh_count(mh_ctx *ctx, const uint8_t *flags, const int32_t *dims, long long *counts, void *scratch,
+                        size_t scratch_bytes, void *stream);
+int mh_carve_mesh(mh_ctx *ctx, const uint8_t *flags, const double *voxel_min, double voxel_size, const int32_t *dims,
+                  long long n_vertices, long long n_triangles, float *vertices, int32_t *faces, void *scratch,
+                  size_t scratch_bytes, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

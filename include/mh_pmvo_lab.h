@@ -25,7 +25,10 @@ extern "C" {
  *   "taps_tile": points per wave of the fp32 front end (mh_project_taps2_kernel): 64 (default; any other value) gives the
  *       fastest iteration, 32 / 16 the kernel's own best time.
  *   "filter_rows": 1 (default) = mh_filter_points launches of >= 4096 points vote with lane = point (mh_filter_rows_kernel;
- *       the rows whose sums take another order stay with the wave-per-point kernel), 0 = wave per point for every row. */
+ *       the rows whose sums take another order stay with the wave-per-point kernel), 0 = wave per point for every row.
+ *   "carve_early_exit": 1 (default) = mh_carve_inside lets a voxel leave its view loop once n_miss > max_miss (the decision is
+ *       taken: n_miss only grows), 0 = every voxel walks every view.  The flags are the same; 0 exists for the timing record
+ *       (tools/bench_carve.py, profiles/carve_timing.json) and the equality test. */
 int mh_ctx_set_lab_option(mh_ctx *ctx, const char *key, int value);
 
 /* Debug counter of the search's key body (csrc/pmvo_search.hip: mh_tap_key): out[2] = how many (wave, view) visits were

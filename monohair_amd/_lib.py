@@ -103,6 +103,11 @@ _SIGS = {
     "mh_inner_domain": (ci, [vp, vp, vp, vp, ci, vp, vp]),
     "mh_inner_diffuse": (ci, [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mh_inner_resolve": (ci, [vp, vp, ci, vp, vp, vp, ctypes.c_double, vp, ctypes.c_double, vp, vp, vp, vp, vp]),
+    "mh_carve_votes": (ci, [vp, vp, vp, ctypes.c_double, vp, vp, vp]),
+    "mh_carve_inside": (ci, [vp, vp, vp, ctypes.c_double, vp, ci, ci, vp, vp]),
+    "mh_carve_mesh_scratch_bytes": (csz, [vp]),
+    "mh_carve_mesh_count": (ci, [vp, vp, vp, vp, vp, csz, vp]),
+    "mh_carve_mesh": (ci, [vp, vp, vp, ctypes.c_double, vp, cll, cll, vp, vp, vp, csz, vp]),
     "mh_knn_grid":(ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

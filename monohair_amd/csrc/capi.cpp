@@ -204,7 +204,8 @@ static const struct { const char *key; int mh_ctx::*field; bool flag; int hi; co
     {"tap_plane", &mh_ctx::use_tap_plane, true, 0, nullptr},
     {"tap_codes", &mh_ctx::use_codes, true, 0, nullptr},
     {"taps_tile", &mh_ctx::taps_tile, false, 0, nullptr},
-    {"filter_rows", &mh_ctx::filter_rows, true, 0, nullptr}};
+    {"filter_rows", &mh_ctx::filter_rows, true, 0, nullptr},
+    {"carve_early_exit", &mh_ctx::carve_early_exit, true, 0, nullptr}};
 
 extern "C" int mh_ctx_set_option(mh_ctx *ctx, const char *key, int value) {
     if (!ctx || !key) return fail(MH_ERR_ARG, "mh_ctx_set_option: bad arguments");

@@ -4,21 +4,6 @@
 
 #include "mh_capi.h"
 
-static bool vol_dims_ok(const int32_t *dims) { return dims && cells_fit_int32(dims[0], dims[1], dims[2]); }
-
-// the one place that fills an MhVolGrid; bust_to_origin: null = no shift.  false: an argument is missing or not usable
-static bool vol_grid(MhVolGrid *gr, const double *voxel_min, double voxel_size, const int32_t *dims,
-                     const double *bust_to_origin = nullptr) {
-    if (!voxel_min || !vol_dims_ok(dims) || !(voxel_size > 0.0 && std::isfinite(voxel_size))) return false;
-    for (int c = 0; c < 3; ++c) {
-        gr->bust[c] = bust_to_origin ? bust_to_origin[c] : 0.0, gr->vmin[c] = voxel_min[c];
-        if (!std::isfinite(gr->bust[c]) || !std::isfinite(voxel_min[c])) return false;
-    }
-    gr->vs = voxel_size;
-    gr->X = dims[0], gr->Y = dims[1], gr->Z = dims[2];
-    return true;
-}
-
 extern "C" int mh_strand_volume_accumulate(mh_ctx *ctx, const float *points, const long long *offsets, int n_strands,
                                            int n_points, const double *bust_to_origin, const double *voxel_min,
                                            double voxel_size, const int32_t *dims, int sub, long long *acc, uint8_t *occ,

@@ -21,13 +21,6 @@
 #include "mh_front.h"
 #include "mh_volume.h"
 
-// the float32 world centre of voxel (x, y, z): the inverse of p2v, evaluated in float64 and rounded once
-__device__ __forceinline__ void mh_fill_centre(const MhVolGrid &gr, int x, int y, int z, float &X0, float &X1, float &X2) {
-    X0 = (float)(gr.vmin[0] + (double)x * gr.vs);
-    X1 = (float)(-(gr.vmin[1] + (double)y * gr.vs));
-    X2 = (float)(-(gr.vmin[2] + (double)z * gr.vs));
-}
-
 // counts [nvox][4] = n_in, n_vis, n_front, n_bad
 __global__ __launch_bounds__(256) void mh_inner_votes_kernel(MhViews vw, const float *__restrict__ bust, MhVolGrid gr,
                                                              int32_t *__restrict__ counts) {

@@ -3,6 +3,7 @@
 // surface: all of it has hidden visibility.
 // capi_host.cpp, which must build without HIP, does not include this file; it defines fail().
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -91,6 +92,7 @@ struct mh_ctx {
     int reproject_fma_min_cols = 28445;   // columns (S x group) from which MKL's threaded sgemm (fma chain) takes over
     int sum_block = 32;       // ATen's outer sum adds the trailing (columns mod 32) of a batch in row_sum order; 0: never
     int topk_order = 0;       // 0: torch.topk's CPU tie order (mh_topk_wave.h); 1: value desc, view asc (round 1's rule)
+    int carve_early_exit = 1; // lab "carve_early_exit": 1 = mh_carve_inside leaves a voxel's view loop once n_miss > max_miss, 0 = all views
     int filter_rows = 1;      // lab "filter_rows": 1 = votes of large launches with lane = point (mh_filter_rows_kernel), 0 = wave per point
     int taps_tile = 1;        // points per wave of mh_project_taps2_kernel: 16 / 32 (A/B), anything else = 64 (default)
     int line_rule = 0;        // strand renderer: 0 GL's diamond-exit, 1 every touched diamond (SwiftShader)
@@ -112,6 +114,22 @@ int launched(int rc, const char *what);        // capi.cpp: a launcher's return 
 // a grid of x * y * z cells that an int32 can index: every dimension at least 1, fewer than 2^31 cells
 inline bool cells_fit_int32(int x, int y, int z) {
     return x >= 1 && y >= 1 && z >= 1 && (long long)x * y < (1ll << 31) && (long long)x * y * z < (1ll << 31);
+}
+
+// ---- the voxel grid of the volume entry points (capi_volume.cpp, capi_carve.cpp)
+inline bool vol_dims_ok(const int32_t *dims) { return dims && cells_fit_int32(dims[0], dims[1], dims[2]); }
+
+// the one place that fills an MhVolGrid; bust_to_origin: null = no shift.  false: an argument is missing or not usable
+inline bool vol_grid(MhVolGrid *gr, const double *voxel_min, double voxel_size, const int32_t *dims,
+                     const double *bust_to_origin = nullptr) {
+    if (!voxel_min || !vol_dims_ok(dims) || !(voxel_size > 0.0 && std::isfinite(voxel_size))) return false;
+    for (int c = 0; c < 3; ++c) {
+        gr->bust[c] = bust_to_origin ? bust_to_origin[c] : 0.0, gr->vmin[c] = voxel_min[c];
+        if (!std::isfinite(gr->bust[c]) || !std::isfinite(voxel_min[c])) return false;
+    }
+    gr->vs = voxel_size;
+    gr->X = dims[0], gr->Y = dims[1], gr->Z = dims[2];
+    return true;
 }
 
 // ---- what the entry points of the strand tools share (capi_capture.cpp, capi_reproj.cpp, capi_volume.cpp)

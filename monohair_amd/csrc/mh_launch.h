@@ -364,4 +364,12 @@ int mh_launch_inner_diffuse(const long long *ext_voxels, const float *ext_ori, i
                             int32_t *status, hipStream_t st);
 int mh_launch_inner_resolve(const long long *dom_voxels, int n_dom, const double *tensor, const uint8_t *known, MhVolGrid gr,
                             double min_coh, float *world, float *ori, double *coh, uint8_t *emit, hipStream_t st);
+// haircarve.hip
+int mh_launch_carve_votes(MhViews vw, const float *bust, MhVolGrid gr, int32_t *counts, hipStream_t st);
+int mh_launch_carve_inside(MhViews vw, const float *bust, MhVolGrid gr, int min_free, int max_miss, int early_exit,
+                           uint8_t *flags, hipStream_t st);
+size_t mh_carve_mesh_scratch_bytes_impl(int X, int Y, int Z);
+int mh_launch_carve_mesh_count(const uint8_t *flags, int X, int Y, int Z, void *scratch, long long *counts, hipStream_t st);
+int mh_launch_carve_mesh(const uint8_t *flags, MhVolGrid gr, void *scratch, long long n_vertices, long long n_triangles,
+                         float *vertices, int32_t *faces, hipStream_t st);
 }

@@ -19,21 +19,13 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, gridviews
 from ._lib import host_ptr
-from .hairvolume import grid_dims3, load_side
+from .hairvolume import load_side
 from .pmvo_utils import GRID_RESOLUTION, VOXEL_MIN, VOXEL_SIZE
 from .timing import stage
 
 MAX_SWEEPS = 1024
-
-
-def _grid(voxel_min, voxel_size, grid_resolution):
-    vmin = np.ascontiguousarray(np.asarray(voxel_min, dtype=np.float64).reshape(-1))
-    vs = float(voxel_size)
-    if vmin.shape != (3,) or not (np.isfinite(vmin).all() and vs > 0.0 and math.isfinite(vs)):
-        raise ValueError("voxel_min is three finite numbers, voxel_size a positive one")
-    return vmin, vs, grid_dims3(grid_resolution)
 
 
 def _voxel_list(voxels):
@@ -41,30 +33,6 @@ def _voxel_list(voxels):
     if v.shape[0] >= 1 << 31:
         raise ValueError("more than 2^31 - 1 voxels")
     return v
-
-
-def _bust_planes(pmvo, bust):
-    """float32 [V,H,W] on the device: the planes themselves, or (vertices, faces) drawn per view of `pmvo` at pixel centre 0"""
-    H, W = pmvo.image_size
-    if isinstance(bust, (tuple, list)) and len(bust) == 2:
-        from .camera import camera_records
-        from .render import DepthRenderer
-
-        if pmvo.camera_dict is None:
-            raise ValueError("a bust mesh needs the cameras of the PMVO object: pass the planes instead")
-        r = DepthRenderer([bust], pmvo.device)
-        recs = camera_records(pmvo.camera_dict)
-        planes = torch.empty((len(recs), H, W), dtype=torch.float32, device=pmvo.device)
-        for i in range(len(recs)):
-            r.render(recs[i], H, W, 0.0, out=planes[i])
-        torch.cuda.current_stream().synchronize()      # (the renderer's scratch is read asynchronously)
-        bust = planes
-    if not torch.is_tensor(bust):
-        bust = torch.from_numpy(np.ascontiguousarray(bust, dtype=np.float32))
-    bust = bust.to(pmvo.device, torch.float32).contiguous()
-    if tuple(bust.shape) != (pmvo.num_view, H, W):
-        raise ValueError("bust planes %r, the views are %r" % (tuple(bust.shape), (pmvo.num_view, H, W)))
-    return bust
 
 
 # ------------------------------------------------------------------------------------------------- 1. domain votes
@@ -80,9 +48,9 @@ def inner_votes(pmvo, bust_planes, grid_resolution=GRID_RESOLUTION, voxel_min=VO
     """The four vote counts of every voxel centre over the views of `pmvo` (a PMVO object of fp32 planes or 8-bit codes).
     bust_planes: float32 [V,H,W], the depth of the bust alone in PMVO's convention, 255 where there is none (or (vertices,
     faces), drawn here).  -> int32 [X,Y,Z,4] = n_in, n_vis, n_front, n_bad."""
-    vmin, vs, dims = _grid(voxel_min, voxel_size, grid_resolution)
+    vmin, vs, dims = gridviews.grid(voxel_min, voxel_size, grid_resolution)
     with torch.cuda.device(pmvo.device):
-        counts = _votes_dev(pmvo, _bust_planes(pmvo, bust_planes), vmin, vs, dims)
+        counts = _votes_dev(pmvo, gridviews.bust_planes(pmvo, bust_planes), vmin, vs, dims)
         return counts.cpu().numpy().reshape(int(dims[0]), int(dims[1]), int(dims[2]), 4)
 
 
@@ -123,9 +91,9 @@ def inner_domain(pmvo, bust_planes, ext_voxels=None, grid_resolution=GRID_RESOLU
                  voxel_size=VOXEL_SIZE, max_bad=0):
     """The voxels to fill: n_in >= 1, n_vis <= 2, n_front >= 1, n_bad <= max_bad and not one of ext_voxels (int [G,3], unique,
     inside the grid).  -> int64 [D,3] (x, y, z) ascending by (x*Y + y)*Z + z."""
-    vmin, vs, dims = _grid(voxel_min, voxel_size, grid_resolution)
+    vmin, vs, dims = gridviews.grid(voxel_min, voxel_size, grid_resolution)
     with torch.cuda.device(pmvo.device):
-        bust = _bust_planes(pmvo, bust_planes)
+        bust = gridviews.bust_planes(pmvo, bust_planes)
         with stage("hairfill: votes", pmvo.device):
             counts = _votes_dev(pmvo, bust, vmin, vs, dims)
         with stage("hairfill: domain", pmvo.device):
@@ -141,7 +109,7 @@ def diffuse_orientation(ext_voxels, ext_ori, domain_voxels, grid_resolution=GRID
     direction, 1.0 of the emitted rows (known, trace > 0, coh >= min_coh) in domain order; with return_details also a dict of
     tensor float64 [D,6], known uint8 [D], depth int32 [D], coh float64 [D], ori float32 [D,3], world float32 [D,3], emit
     uint8 [D], ext_tensor float64 [G,6], ext_source uint8 [G]."""
-    vmin, vs, dims = _grid(voxel_min, voxel_size, grid_resolution)
+    vmin, vs, dims = gridviews.grid(voxel_min, voxel_size, grid_resolution)
     ev, dv = _voxel_list(ext_voxels), _voxel_list(domain_voxels)
     eo = np.ascontiguousarray(np.asarray(ext_ori, dtype=np.float32).reshape(-1, 3))
     if ev.shape[0] != eo.shape[0]:

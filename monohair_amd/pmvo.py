@@ -188,7 +188,7 @@ class PMVO:
         except Exception:
             pass
 
-    LAB_OPTIONS = ("search_variant", "search_body", "tap_plane", "tap_codes", "taps_tile", "filter_rows")
+    LAB_OPTIONS = ("search_variant", "search_body", "tap_plane", "tap_codes", "taps_tile", "filter_rows", "carve_early_exit")
 
     def set_option(self, key, value):
         """A supported option of the context (include/mh_pmvo.h: reproject_rule, reproject_fma_min_cols, sum_block, topk_order,
