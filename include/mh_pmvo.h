@@ -848,6 +848,67 @@ int mh_carve_mesh(mh_ctx *ctx, const uint8_t *flags, const double *voxel_min, do
                   long long n_vertices, long long n_triangles, float *vertices, int32_t *faces, void *scratch,
                   size_t scratch_bytes, void *stream);
 
+/* Photo-consistent carve (monohair_amd.hairstereo; no counterpart in the reference): a second carve pass over candidate
+ * voxels, by the agreement of the capture's gray photographs across neighbouring views.  The conventions are those of
+ * "Silhouette carve" and "Inner fill": voxel_min [3] and voxel_size are HOST float64 (finite, voxel_size > 0), dims = (X, Y, Z)
+ * HOST int32 with X*Y*Z < 2^31, a voxel's linear index is (x*Y + y)*Z + z, its centre w and the projection of w are those of
+ * "Inner fill" part 1 (the same device functions, csrc/mh_volume.h and csrc/mh_front.h), and the float32 comparisons are those
+ * of the vote kernels.  Only the cameras and the mask planes of the context are read.  Everything after the projection is
+ * integer arithmetic, so the result does not depend on any order of evaluation.  Host ints: cell (1 <= cell <= 256), radius in
+ * {1, 2, 3}, K = n_neighbours (1 <= K <= 8), keep (1 <= keep <= K), max_cost >= 0, min_agree >= 1, min_through >= 1; host
+ * float32 m255 (finite, >= 0), a margin on the scale of the depth planes (z255).  The rule has five parts.
+ *
+ * 1. Reduced images and census codes, of gray: uint8 [V,H,W].  Hc = ceil(H / cell), Wc = ceil(W / cell); block (i, j) holds the
+ *   pixels (row, col) of the image with row / cell == i and col / cell == j (integer division), n of them (fewer than cell^2 at
+ *   the lower and right borders), and g[v,i,j] = (2*sum + n) / (2*n) in integers, sum being the sum of the block's pixels: the
+ *   mean rounded half up, a uint8.  With B = (2*radius + 1)^2 - 1, bit b of census[v,i,j] (a uint64, bits B and above zero)
+ *   is g[v, clamp(i + dy, 0, Hc - 1), clamp(j + dx, 0, Wc - 1)] < g[v,i,j], the offsets (dy, dx) running row-major from
+ *   (-radius, -radius) to (radius, radius) with the centre left out: b = 0 is (-radius, -radius), b = B - 1 is (radius, radius).
+ * 2. Per (voxel w, view v) terms.  The view abstains, and otherwise free, hair, the rounded and clamped pixel (row, col) and
+ *   z255 are formed, exactly as in "Silhouette carve" part 1.  The view TAKES PART in w iff it does not abstain and w is both
+ *   free and hair there.  The voxel's cell in the view is (row / cell, col / cell).
+ * 3. Cost and winners.  neighbours: int32 [V,K]; row r lists the neighbour views of view r, an entry outside [0, V) (-1 by
+ *   convention) is none; a row never names r itself (an entry that does is none as well; the Python layer refuses such a
+ *   table).  For a candidate voxel w and a view r that takes part in w, h_n = popcount(census[r, cell of w in r] ^ census[n,
+ *   cell of w in n]) for every entry n of row r that takes part in w (an n listed twice counts twice).  With fewer than keep
+ *   such n the pair (w, r) has no cost.  Otherwise S = the sum of the keep smallest h_n and cost = (1024 * S) / (B * keep) in
+ *   integers (at most 1024).  The WINNER of (r, cell) is the minimum, over the candidates w that have a cost in r and lie in
+ *   that cell, of the uint64 key (cost << 32) | linear index of w: the lowest cost, among equal costs the lowest index.  A
+ *   cell without such a candidate holds all ones.
+ * 4. Agreement.  A cell's key is VALID iff it is not all ones, its cost (key >> 32) is <= max_cost and its index (the low 32
+ *   bits) is below X*Y*Z; w* is then the voxel of that index and z255_r(w*) its z255 in view r, projected again by the same
+ *   function.  agree[w] of a candidate w is the number of views r that take part in w, whose cell of w holds a valid key, and
+ *   in which |z255_r(w) - z255_r(w*)| <= m255 (the float32 difference, its absolute value, the float32 comparison).  A winner
+ *   agrees with itself.  agree of a voxel that is no candidate is 0.
+ * 5. Refinement.  through[w] of a candidate w is the number of views r that do not abstain and in which w is free (hair or
+ *   not), whose cell of w holds a valid key with agree[w*] >= min_agree, and in which z255_r(w) + m255 < z255_r(w*) (the
+ *   float32 sum, the float32 comparison): w lies in front of a confirmed winner by more than the margin.  refined[w] = 1 iff w
+ *   is a candidate and through[w] < min_through, else 0.  The stereo depth of (r, cell) is z255_r(w*) of a valid key with
+ *   agree[w*] >= min_agree, else 255.
+ *
+ * mh_stereo_census: gray [n_views, height, width] uint8 on the device (any context: nothing of it is read) -> reduced
+ *   [n_views, Hc, Wc] uint8 = g and census [n_views, Hc, Wc] uint64.
+ * mh_stereo_winners: the views of ctx are V x H x W; bust [V,H,W] float32 as for the carve; candidates [n_candidates] int32, the
+ *   linear indices of the candidate voxels in any order, each at most once (an index outside the grid is skipped; the Python
+ *   layer compacts the flags with mh_select_rows); census [V,Hc,Wc] of part 1 for the same cell and radius; neighbours [V,K]
+ *   int32 on the device -> keys [V,Hc,Wc] uint64, every cell written (all ones first, then a 64-bit atomic minimum per
+ *   (candidate, view) with a cost: the one place the rule's minimum needs an atomic).  n_candidates = 0 gives all ones.
+ * mh_stereo_agree: flags [X*Y*Z] uint8 (non-zero = candidate), keys of mh_stereo_winners -> agree [X*Y*Z] int32.
+ * mh_stereo_refine: -> refined [X*Y*Z] uint8 and depth [V,Hc,Wc] float32.  agree is read at the index of a valid key only.
+ * Nothing but the stated outputs is written; no entry point synchronises with the host. */
+int mh_stereo_census(mh_ctx *ctx, const uint8_t *gray, int n_views, int height, int width, int cell, int radius,
+                     uint8_t *reduced, unsigned long long *census, void *stream);
+int mh_stereo_winners(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                      const int32_t *candidates, int n_candidates, const unsigned long long *census,
+                      const int32_t *neighbours, int n_neighbours, int cell, int radius, int keep, unsigned long long *keys,
+                      void *stream);
+int mh_stereo_agree(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                    const uint8_t *flags, const unsigned long long *keys, int cell, int max_cost, float m255, int32_t *agree,
+                    void *stream);
+int mh_stereo_refine(mh_ctx *ctx, const float *bust, const double *voxel_min, double voxel_size, const int32_t *dims,
+                     const uint8_t *flags, const unsigned long long *keys, const int32_t *agree, int cell, int max_cost,
+                     float m255, int min_agree, int min_through, uint8_t *refined, float *depth, void *stream);
+
 /* ---- the one exchange of the data path, RCCL over xGMI.  The reference has no multi-GPU path
  * (options.py:112 asserts a single GPU); the voxel fit of refine (PMVO.py:695-726) is sharded here by x-slabs of
  * the volume, every rank fitting the voxels of its slab into a zero-initialised dense [X,Y,Z,C] fp32 volume (C = 4:

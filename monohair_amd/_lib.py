@@ -108,6 +108,10 @@ _SIGS = {
     "mh_carve_mesh_scratch_bytes": (csz, [vp]),
     "mh_carve_mesh_count": (ci, [vp, vp, vp, vp, vp, csz, vp]),
     "mh_carve_mesh": (ci, [vp, vp, vp, ctypes.c_double, vp, cll, cll, vp, vp, vp, csz, vp]),
+    "mh_stereo_census": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "mh_stereo_winners": (ci, [vp, vp, vp, ctypes.c_double, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "mh_stereo_agree": (ci, [vp, vp, vp, ctypes.c_double, vp, vp, vp, ci, ci, cf, vp, vp]),
+    "mh_stereo_refine": (ci, [vp, vp, vp, ctypes.c_double, vp, vp, vp, vp, ci, ci, cf, ci, ci, vp, vp, vp]),
     "mh_knn_grid":(ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
     "mh_nearest_distance": (ci, [vp, vp, ci, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]),
     "mh_points_bbox": (ci, [vp, vp, ci, vp, vp]),

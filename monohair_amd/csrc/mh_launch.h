@@ -372,4 +372,15 @@ size_t mh_carve_mesh_scratch_bytes_impl(int X, int Y, int Z);
 int mh_launch_carve_mesh_count(const uint8_t *flags, int X, int Y, int Z, void *scratch, long long *counts, hipStream_t st);
 int mh_launch_carve_mesh(const uint8_t *flags, MhVolGrid gr, void *scratch, long long n_vertices, long long n_triangles,
                          float *vertices, int32_t *faces, hipStream_t st);
+// hairstereo.hip
+int mh_launch_stereo_census(const uint8_t *gray, int V, int H, int W, int cell, int radius, uint8_t *reduced,
+                            unsigned long long *census, hipStream_t st);
+int mh_launch_stereo_winners(MhViews vw, const float *bust, MhVolGrid gr, const int32_t *cand, int n_cand,
+                             const unsigned long long *census, const int32_t *nb, int K, int cell, int radius, int keep,
+                             unsigned long long *keys, hipStream_t st);
+int mh_launch_stereo_agree(MhViews vw, const float *bust, MhVolGrid gr, const uint8_t *flags, const unsigned long long *keys,
+                           int cell, int max_cost, float m255, int32_t *agree, hipStream_t st);
+int mh_launch_stereo_refine(MhViews vw, const float *bust, MhVolGrid gr, const uint8_t *flags, const unsigned long long *keys,
+                            const int32_t *agree, int cell, int max_cost, float m255, int min_agree, int min_through,
+                            uint8_t *refined, float *depth, hipStream_t st);
 }
