@@ -9,8 +9,12 @@ index (x*8 + y)*2 + z.  The neighbour table NB gives view 4 no neighbour, views 
 The images are flat (100) except where a case needs a census code; with radius 1 (B = 8 bits, offsets (-1,-1) (-1,0) (-1,1)
 (0,-1) (0,1) (1,-1) (1,0) (1,1) = bits 0..7) a pixel brighter than its eight neighbours has the code 0xFF and leaves theirs 0.
 
+hand_scene_wide has tables of four (HAND_NB4) and seven (HAND_NB7) columns and census codes whose distances are known by hand.
+
 2. The textured sphere: 12 views of 48 x 48 on a ring round a sphere whose images are evaluated analytically from the
-ray-sphere intersection through a seeded smooth 3D texture, with a grid of 32^3 voxels of 1/128; a control with a texture of its own per view."""
+ray-sphere intersection through a seeded smooth 3D texture, with a grid of 32^3 voxels of 1/128; a control with a texture of
+its own per view; neighbour tables of any width with shuffled columns (sphere_table); a thirteenth view inside the grid
+(inside_cameras)."""
 import numpy as np
 
 import hair_fill_cases as C
@@ -109,6 +113,102 @@ def hand_scene_two():
     return dict(gray=gray, mask=mask, bust=bust, flags=flags, keys=keys, cell=2, radius=1, keep=2, w=(0, 0, 0), star=(0, 1, 1),
                 u=(1, 1, 0), margins=dict(zero=F(0), on=GAP, rounds_to_on=np.nextafter(GAP, F(0)), sum_below=sum_below,
                                           sum_above=sum_above))
+
+
+# Wider neighbour tables for hand_scene_wide.  NB4: every A row names the other four A views, in an order chosen per row; the B
+# rows are padded with -1 (before, between and behind the entries), and row 7 names view 5 twice.  NB7: every row names the other
+# seven views, in an order of its own.
+HAND_NB4 = np.array([[1, 2, 3, 4], [4, 0, 3, 2], [0, 1, 3, 4], [0, 1, 2, 4], [0, 1, 2, 3],
+                     [6, 7, -1, -1], [-1, 5, -1, 7], [5, 5, 6, -1]], np.int32)
+HAND_NB7 = np.array([[(r + s) % 8 for s in (3, 1, 7, 5, 2, 6, 4)] for r in range(8)], np.int32)
+
+
+def hand_scene_wide():
+    """cell 1, radius 1, for the tables of four and of seven columns.  Every voxel is a candidate; in each cell the layer-0
+    voxel wins on the index, as both layers have the cell's cost.  Three pixels carry census codes:
+
+    P = (row 1, col 5), the voxels (5, 1, .), seen by the A views alone.  Codes of the views 0..4: 0x00, 0x01, 0x07, 0x3F, 0xFF
+    (0, 1, 3, 6 and 8 bits, each set of bits inside the next), so the distance of two views is the difference of their bit
+    counts.  In the order of NB4 the four distances arrive
+        view 0, [1, 2, 3, 4]: 1 3 6 8 (ascending)        view 1, [4, 0, 3, 2]: 7 1 5 2
+        view 2, [0, 1, 3, 4]: 3 2 3 5 (two equal)        view 3, [0, 1, 2, 4]: 6 5 3 2 (descending)
+        view 4, [0, 1, 2, 3]: 8 7 5 2 (descending)
+    Q = (row 6, col 1), the voxels (1, 6, .): view 2 sees no hair there and view 4 has the code 0xFF, the rest 0.  Three of a
+    row's four neighbours take part: exactly keep for keep = 3, one fewer than keep for keep = 4.
+    M = (row 4, col 4), the voxels (4, 4, .), which all eight views see: view 0 has the code 0xFF, view 5 0x03, view 6 0x01, the
+    rest 0.
+
+    -> dict(gray, mask, bust, flags, keys4: {keep: {(view, row, col): key}} for NB4, keys7: the same for NB7, codes: {(view,
+    row, col): census code})"""
+    gray = np.full((V_HAND, 8, 8), 100, np.uint8)
+    dark = {1: [(0, 4)], 2: [(0, 4), (0, 5), (0, 6)], 3: [(0, 4), (0, 5), (0, 6), (1, 4), (1, 6), (2, 4)]}      # bits 0.. of P
+    for v, pixels in dark.items():
+        for p in pixels:
+            gray[(v,) + p] = 90
+    gray[4, 1, 5] = gray[4, 6, 1] = gray[0, 4, 4] = 110
+    gray[5, 3, 3] = gray[5, 3, 4] = gray[6, 3, 3] = 90          # bits 0 and 1 of M in view 5, bit 0 in view 6
+    mask = np.ones((V_HAND, 8, 8), F)
+    mask[2, 6, 1] = 0.0
+    bust = np.full((V_HAND, 8, 8), 255.0, F)
+    flags = np.ones((8, 8, 2), np.uint8)
+    codes = {(0, 1, 5): 0x00, (1, 1, 5): 0x01, (2, 1, 5): 0x07, (3, 1, 5): 0x3F, (4, 1, 5): 0xFF,
+             (4, 6, 1): 0xFF, (0, 6, 1): 0, (1, 6, 1): 0, (3, 6, 1): 0,
+             (0, 4, 4): 0xFF, (5, 4, 4): 0x03, (6, 4, 4): 0x01, (1, 4, 4): 0, (2, 4, 4): 0, (3, 4, 4): 0, (4, 4, 4): 0,
+             (7, 4, 4): 0}
+    p, q, m = (5, 1, 0), (1, 6, 0), (4, 4, 0)
+    # the key is 1024 * S // (8 * keep), S the sum of the keep smallest distances
+    k4 = {
+        1: {(0, 1, 5): key(128, *p), (4, 1, 5): key(256, *p), (2, 1, 5): key(256, *p),          # 1024 * 1 // 8, 1024 * 2 // 8
+            (7, 4, 4): key(128, *m)},                                                             # 2 2 1 -> 1
+        2: {(0, 1, 5): key(256, *p), (4, 1, 5): key(448, *p), (2, 1, 5): key(320, *p),          # 4, 7 and 5 of 16
+            (5, 4, 4): key(192, *m),                                                              # view 5, [6, 7]: 1 2 -> 3 of 16
+            (7, 4, 4): key(192, *m)},                                                             # 1 + 2
+        3: {
+            (0, 1, 5): key(426, *p),          # 1 + 3 + 6 = 10: 10240 // 24
+            (1, 1, 5): key(341, *p),          # 1 + 2 + 5 = 8: 8192 // 24
+            (2, 1, 5): key(341, *p),          # 2 + 3 + 3 = 8: the equal pair counts twice
+            (3, 1, 5): key(426, *p),          # 2 + 3 + 5 = 10
+            (4, 1, 5): key(597, *p),          # 2 + 5 + 7 = 14: 14336 // 24
+            # Q: exactly keep neighbours take part.  Views 0, 1 and 3: 0 0 8 -> 8; view 4: 8 8 8 -> 24; view 2 sees no hair
+            (0, 6, 1): key(341, *q), (1, 6, 1): key(341, *q), (3, 6, 1): key(341, *q), (4, 6, 1): key(1024, *q), (2, 6, 1): NONE,
+            # M.  View 0 against four flat views: 8 8 8; view 1, [4, 0, 3, 2]: 0 8 0 0 -> 0
+            (0, 4, 4): key(1024, *m), (1, 4, 4): key(0, *m),
+            (5, 4, 4): NONE, (6, 4, 4): NONE,          # two neighbours take part: keep - 1
+            # view 7, [5, 5, 6, -1]: view 5 counts twice, have = 3: 2 + 2 + 1 = 5: 5120 // 24
+            (7, 4, 4): key(213, *m),
+            (0, 0, 0): key(0, 0, 0, 0), (5, 0, 0): NONE,
+        },
+        4: {
+            (0, 1, 5): key(576, *p),          # 18: 18432 // 32
+            (1, 1, 5): key(480, *p),          # 1 + 2 + 5 + 7 = 15
+            (2, 1, 5): key(416, *p),          # 2 + 3 + 3 + 5 = 13
+            (3, 1, 5): key(512, *p),          # 16
+            (4, 1, 5): key(704, *p),          # 22
+            # Q: keep - 1 neighbours take part
+            (0, 6, 1): NONE, (1, 6, 1): NONE, (2, 6, 1): NONE, (3, 6, 1): NONE, (4, 6, 1): NONE,
+            (0, 4, 4): key(1024, *m), (1, 4, 4): key(256, *m),          # 0 0 0 8 -> 8192 // 32
+            (5, 4, 4): NONE, (6, 4, 4): NONE, (7, 4, 4): NONE,          # view 7: have = 3
+            (0, 0, 0): key(0, 0, 0, 0),
+        },
+    }
+    k7 = {
+        7: {
+            # M, all seven neighbours take part.  View 5 (0x03): view 0: 6, views 1..4 and 7: 2 each, view 6: 1 -> 17: 17408 // 56
+            (5, 4, 4): key(310, *m),
+            # view 0 (0xFF): views 1..4 and 7: 8 each, view 5: 6, view 6: 7 -> 53: 54272 // 56
+            (0, 4, 4): key(969, *m),
+            # view 7 (0): 8 0 0 0 0 2 1 -> 11: 11264 // 56
+            (7, 4, 4): key(201, *m),
+            # P and a flat pixel: the four other A views take part, the B views do not
+            (0, 1, 5): NONE, (4, 1, 5): NONE, (0, 0, 0): NONE,
+        },
+        4: {
+            (0, 1, 5): key(576, *p), (4, 1, 5): key(704, *p), (2, 1, 5): key(416, *p),          # as under NB4: the same four
+            (0, 6, 1): NONE,                                                                    # three take part
+            (5, 4, 4): key(224, *m),          # the four smallest of 6 2 2 2 2 1 2: 1 + 2 + 2 + 2 = 7: 7168 // 32
+        },
+    }
+    return dict(gray=gray, mask=mask, bust=bust, flags=flags, keys4=k4, keys7=k7, codes=codes, cell=1, radius=1)
 
 
 def census_image():
@@ -218,6 +318,48 @@ def sphere_neighbours(k=2):
         order = sorted((round(d[r, n], 9), n) for n in range(SPHERE_V) if n != r)
         out[r] = [n for _, n in order[:k]]
     return out
+
+
+def sphere_table(k, keep, seed=0):
+    """sphere_neighbours(k) with the columns of every row in a seeded order of the row's own, so that the distances do not
+    arrive nearest view first; row 3 is padded with -1 down to `keep` entries and row 8 down to keep - 1"""
+    rng = np.random.default_rng([43, k, keep, seed])
+    nb = sphere_neighbours(k)
+    nb = np.stack([row[rng.permutation(k)] for row in nb]).astype(np.int32)
+    for row, valid in ((3, keep), (8, keep - 1)):
+        gone = rng.permutation(k)[:k - valid]
+        nb[row, gone] = -1
+    return nb
+
+
+INSIDE_VIEW = SPHERE_V          # the index of the view of inside_cameras that sits inside the grid
+
+
+def inside_cameras():
+    """the twelve ring cameras and a thirteenth inside the grid: the pose of ring view 0 (it looks down -x) with its centre at
+    x = SPHERE_VS / 2, which is the plane of the voxel centres x = 16 (world x = (16 - 15.5) / 128): those 32 x 32 centres have
+    z' = 0 exactly, the 15 layers x = 17..31 lie behind the view, the 16 layers x = 0..15 in front of it.  Its focal length of 2
+    is short enough for the pixels of many voxels behind it to fall inside the image."""
+    cams = sphere_cameras()
+    c2w = np.array(cams[0]["pose"])
+    c2w[:3, 3] = (0.5 * SPHERE_VS, 0.0, 0.0)
+    cams.append(dict(file="inside_00", pose=c2w.tolist(), ndc_prj=[2.0, 2.0, 0.0, 0.0]))
+    return cams
+
+
+def inside_views():
+    """-> (gray, mask) of sphere_views() with the thirteenth view's planes behind them: a flat gray image, hair everywhere"""
+    gray, mask, _ = sphere_views()
+    H = W = SPHERE_HW
+    return (np.concatenate([gray, np.full((1, H, W), 128, np.uint8)]), np.concatenate([mask, np.ones((1, H, W), F)]))
+
+
+def inside_table():
+    """int32 [13,3]: the three nearest ring views of each ring view, with view 12 in place of the third in the rows of the views 0
+    and 6; view 12 itself has the neighbours 0, 6 and 3"""
+    nb = np.concatenate([sphere_neighbours(3), np.array([[0, 6, 3]], np.int32)])
+    nb[0, 2] = nb[6, 2] = INSIDE_VIEW
+    return nb
 
 
 def sphere_world():

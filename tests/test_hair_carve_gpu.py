@@ -3,7 +3,9 @@
 tests/hair_fill_cases.py and on the seeded scene of the inner fill's tests (24 views of 32 x 64, the cameras of
 tests/border_cases.py) for grids of 12 x 14 x 16 and 33 x 17 x 65 voxels, through a context of fp32 planes and one of 8-bit
 codes, and against the columns of mh_inner_votes; the INSIDE flags of both forms of the kernel; the mesh of seeded and counted
-flags, bytewise, into buffers with guard rows; the API and the command."""
+flags, bytewise, into buffers with guard rows; the votes and flags of a scene one of whose views sits inside the grid, on the
+plane of a layer of voxel centres; the API and the command.  (Grids whose mesh scans take several batches:
+tests/test_hair_carve_scan_gpu.py.)"""
 import os
 
 import numpy as np
@@ -12,6 +14,7 @@ import pytest
 import hair_carve_np as R
 import hair_fill_cases as C
 from test_hair_fill_gpu import GRIDS as FILL_GRIDS, seeded as fill_seeded          # noqa: F401  (a fixture of that file)
+from test_hair_stereo_host import inside                                           # noqa: F401  (a fixture of that file)
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +133,34 @@ def test_votes_and_flags_on_the_seeded_scene(seeded, grid, kind):
             seen.add(int(want.sum()))
     # (on the coarse grid every voxel has n_free >= 2: min_free 1 and 2 decide alike there)
     assert len(seen) == (9 if grid == "33x17x65" else 6) and 0 not in seen and len(c) not in seen
+
+
+@pytest.mark.parametrize("kind", ["fp32", "u8"])
+def test_votes_and_flags_with_a_view_inside_the_grid(inside, kind):
+    """the textured sphere of tests/hair_stereo_cases.py with a thirteenth view on the plane of a layer of voxel centres: 1 024
+    centres have z' = 0 in it, where the projection divides by zero, and 15 360 lie behind it, over a thousand of them with a
+    pixel inside its image (tests/test_hair_stereo_host.py::test_view_inside_the_grid asserts that of the restatement): the
+    view abstains there by the sign of z' alone"""
+    import hair_stereo_cases as S
+    from monohair_amd import haircarve
+    from test_hair_stereo_gpu import contexts
+
+    ctx = contexts(S.inside_cameras(), inside["mask"])[0][kind]
+    grid = (S.SPHERE_DIMS, S.SPHERE_VMIN, S.SPHERE_VS)
+    c = inside["votes"]
+    got = haircarve.carve_votes(ctx, inside["bust"], *grid).reshape(-1, 3)
+    assert np.array_equal(got, c)
+    assert c[:, 0].max() == 13 and c[:, 0].min() < 12
+    seen = set()
+    for min_free, max_miss in ((2, 0), (12, 0), (13, 0), (13, 1)):
+        want = R.inside_flags(c, min_free, max_miss)
+        for early in (0, 1):
+            ctx.set_lab_option("carve_early_exit", early)
+            flags = haircarve.carve_inside(ctx, inside["bust"], *grid, min_free, max_miss)
+            assert np.array_equal(flags.reshape(-1), want), (min_free, max_miss, early)
+        seen.add(int(want.sum()))
+    assert np.array_equal(R.inside_flags(c).reshape(S.SPHERE_DIMS), inside["flags"])
+    assert len(seen) >= 3 and 0 not in seen          # (min_free 13: the voxels the thirteenth view counts as well)
 
 
 # ------------------------------------------------------------------------------------------------- mesh

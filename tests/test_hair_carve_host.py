@@ -132,6 +132,16 @@ def test_full_block_and_its_cavity():
     assert inward == 12
 
 
+def test_full_grid_of_several_scan_batches():
+    """the full 64 x 64 x 33 grid, whose mesh tests/test_hair_carve_scan_gpu.py holds the kernels to: the six sides, and the
+    corners of the grid less those of its interior"""
+    X, Y, Z = 64, 64, 33
+    v, t = _mesh(np.ones((X, Y, Z), np.uint8))
+    assert len(t) == 4 * (X * Y + Y * Z + X * Z) == 33280
+    assert len(v) == (X + 1) * (Y + 1) * (Z + 1) - (X - 1) * (Y - 1) * (Z - 1) == 16642
+    assert t.min() == 0 and t.max() == len(v) - 1 and len(np.unique(v, axis=0)) == len(v)
+
+
 def test_empty_flags():
     v, t = R.mesh(np.zeros((3, 2, 4), np.uint8), VMIN, VS)
     assert v.shape == (0, 3) and t.shape == (0, 3) and v.dtype == F and t.dtype == np.int32

@@ -2,7 +2,9 @@
 (tests/hair_stereo_np.py), bit for bit on every quantity -- the reduced images and census planes, every winner key, the
 agreement counts, the refined flags and the depth planes -- on the hand-made scenes and on the textured sphere of
 tests/hair_stereo_cases.py (scene and control, the hull and the hull with the spike), at candidate counts of 1, 63, 64, 65 and
-257, through a context of fp32 planes and one of 8-bit codes; the refusals; and the refined flags as a mesh."""
+257, through a context of fp32 planes and one of 8-bit codes; neighbour tables of 3 to 8 columns with `keep` up to the table's
+width, whose distances arrive out of order, on a hand-made scene and on the sphere; a thirteenth view inside the sphere's grid,
+with voxel centres on its plane z' = 0 and behind it; the refusals; and the refined flags as a mesh."""
 import numpy as np
 import pytest
 
@@ -10,7 +12,8 @@ import hair_carve_np as CARVE
 import hair_fill_cases as C
 import hair_stereo_cases as S
 import hair_stereo_np as R
-from test_hair_stereo_host import M255, SPHERE, records, sphere          # noqa: F401  (a fixture of that file)
+from test_hair_stereo_host import (INSIDE_KEEPS, M255, SPHERE, WIDE, inside, records, sphere, wide,          # noqa: F401
+                                   wide_conditions)          # (sphere, wide and inside are fixtures of that file)
 
 pytestmark = pytest.mark.gpu
 
@@ -131,6 +134,36 @@ def test_hand_scenes_equal_the_restatement(hand, name, cell, kind):
         assert seen == {3, 5}          # the through test removes w and u, or nothing
 
 
+@pytest.fixture(scope="module")
+def hand_wide():
+    scene = S.hand_scene_wide()
+    ctxs, planes = contexts(C.hand_cameras(), scene["mask"])
+    assert np.array_equal(planes, scene["mask"])
+    return scene, ctxs
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("table,keep", [("keys4", 1), ("keys4", 2), ("keys4", 3), ("keys4", 4), ("keys7", 1), ("keys7", 4),
+                                        ("keys7", 5), ("keys7", 7)])
+def test_hand_scene_with_wide_tables(hand_wide, table, keep, kind):
+    """tables of four and seven columns: the hand-computed keys, and every stage against the restatement"""
+    from monohair_amd import hairstereo
+
+    scene, ctxs = hand_wide
+    nb = S.HAND_NB4 if table == "keys4" else S.HAND_NB7
+    keys = hairstereo.stereo_winners(ctxs[kind], scene["bust"], scene["flags"], scene["gray"], nb, *HAND_GRID, cell=1, radius=1,
+                                     keep=keep)
+    for (r, i, j), k in scene[table].get(keep, {}).items():
+        assert keys[r, i, j] == k, (r, i, j, hex(int(keys[r, i, j])), hex(int(k)))
+    t = R.Terms(records(C.hand_cameras()), scene["mask"], scene["bust"], C.HAND_VMIN, C.HAND_VS, C.HAND_DIMS, 1)
+    for max_cost, m255, min_agree, min_through in [(1024, S.GAP, 3, 3), (426, np.nextafter(S.GAP, F(0)), 2, 1), (341, F(0), 1, 2)]:
+        args = (nb, 1, keep, max_cost, m255, min_agree, min_through)
+        want = reference(t, scene["gray"], scene["flags"], *args)
+        got = run_stages(ctxs[kind], scene["bust"], scene["flags"], scene["gray"], nb, HAND_GRID, 1, *args[1:])
+        same(got, want, (table, keep, max_cost))
+        assert np.array_equal(got["keys"], keys)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_no_candidate_and_flat_images(hand, kind):
     scene, ctxs = hand["one"]
@@ -190,6 +223,57 @@ def test_a_counted_number_of_candidates(sphere, sphere_ctx, count, kind):
         got = run_stages(sphere_ctx[kind], run["bust"], flags, run["gray"], sphere["neighbours"], SPHERE_GRID, cell, *args)
         same(got, want, (count, cell))
         assert int((got["keys"] != S.NONE).sum()) > 0
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("K,keep", WIDE)
+def test_sphere_with_wide_tables_equals_the_restatement(sphere, wide, sphere_ctx, K, keep, kind):
+    """3, 5 and 8 neighbours whose distances do not arrive in order, keep up to K: every slot of the kernel's list is written"""
+    run, w = sphere[(False, "hull")], wide[(K, keep)]
+    wide_conditions(run, w, K, keep)
+    got = run_stages(sphere_ctx[kind], run["bust"], run["flags"], run["gray"], w["nb"], SPHERE_GRID, S.SPHERE_CELL, S.SPHERE_RADIUS,
+                     keep, w["max_cost"], M255, SPHERE["min_agree"], SPHERE["min_through"])
+    same(got, w, (K, keep))
+
+
+def test_stereo_with_five_neighbours_of_which_three_are_kept(sphere, sphere_ctx):
+    from monohair_amd import hairstereo
+
+    run = sphere[(False, "hull")]
+    cams = sphere_ctx["fp32"].camera_dict
+    nb = hairstereo.neighbour_table(cams, 5)
+    # (the two views three steps along the ring are equally far but for the rounding of the records: either is the fifth)
+    assert nb.shape == (S.SPHERE_V, 5) and np.array_equal(np.sort(nb[:, :4], 1), np.sort(S.sphere_neighbours(4), 1))
+    assert all(nb[r, 4] in ((r + 3) % S.SPHERE_V, (r - 3) % S.SPHERE_V) for r in range(S.SPHERE_V))
+    want = R.stereo(sphere["records"], run["gray"], run["mask"], run["bust"], S.SPHERE_VMIN, S.SPHERE_VS, S.SPHERE_DIMS,
+                    run["flags"], nb, S.SPHERE_CELL, S.SPHERE_RADIUS, 3, SPHERE["max_cost"], M255, SPHERE["min_agree"],
+                    SPHERE["min_through"])
+    assert 0 < want["refined"].sum() and (want["depth"] != 255).sum() > 100
+    for kind in KINDS:
+        refined, depth = hairstereo.stereo(sphere_ctx[kind], cams, run["gray"], run["bust"], run["flags"], S.SPHERE_VS,
+                                           S.SPHERE_VMIN, neighbours=5, keep=3, radius=S.SPHERE_RADIUS,
+                                           max_cost=SPHERE["max_cost"], min_agree=SPHERE["min_agree"])
+        assert refined.reshape(-1).tobytes() == want["refined"].tobytes() and depth.tobytes() == want["depth"].tobytes()
+
+
+@pytest.fixture(scope="module")
+def inside_ctx(inside):
+    ctxs, planes = contexts(S.inside_cameras(), inside["mask"])
+    assert np.array_equal(planes, inside["mask"])
+    return ctxs
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("keep", INSIDE_KEEPS)
+def test_a_view_inside_the_grid_equals_the_restatement(inside, inside_ctx, keep, kind):
+    """a thirteenth view on the plane of a layer of voxel centres (z' = 0 there, where the projection divides by zero), with
+    candidates behind it whose pixels lie inside its image: it abstains by the sign of z' alone.  (What the restatement says of
+    the scene is asserted by tests/test_hair_stereo_host.py::test_view_inside_the_grid.)"""
+    want = inside["runs"][keep]
+    got = run_stages(inside_ctx[kind], inside["bust"], inside["flags"], inside["gray"], inside["nb"], SPHERE_GRID, S.SPHERE_CELL,
+                     S.SPHERE_RADIUS, keep, SPHERE["max_cost"], M255, SPHERE["min_agree"], SPHERE["min_through"])
+    same(got, want, keep)
+    assert (got["keys"][S.INSIDE_VIEW] != S.NONE).sum() > 50
 
 
 def test_stereo_runs_the_stages_and_its_flags_make_a_closed_mesh(sphere, sphere_ctx):

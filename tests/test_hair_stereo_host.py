@@ -3,7 +3,10 @@ tests/hair_stereo_cases.py -- reduced images and census codes with windows clamp
 neighbour rows, fewer than `keep` neighbours, equal costs, flat images, no candidate), agreement and refinement on their bounds
 -- and, on the textured sphere, shown to do what the rule is for: against a control whose views share no texture it confirms
 more cells, its confirmed winners lie nearer the analytic depth, and it removes more of a hand-made spike than of the sphere.
-The sphere's assertions fix no figures; the four shares are printed."""
+The sphere's assertions fix no figures; the four shares are printed.  Neighbour tables of four and seven columns on the hand
+cameras, with keys worked out by hand for keep up to 7, and tables of 3, 5 and 8 shuffled columns on the sphere; a thirteenth view
+inside the sphere's grid, with voxel centres on its plane z' = 0 and behind it.  The fixtures `wide` and `inside` hold what the
+GPU tests compare the kernels with."""
 import numpy as np
 import pytest
 
@@ -93,6 +96,29 @@ def test_winner_keys_by_hand(keep):
     # no candidate at all, and candidates outside the grid
     for cand in (np.zeros(0, np.int64), np.array([-1, 128, 1 << 30])):
         assert (R.winners(t, codes, S.HAND_NB, 1, keep, cand) == S.NONE).all()
+
+
+@pytest.mark.parametrize("table,keep", [("keys4", 1), ("keys4", 2), ("keys4", 3), ("keys4", 4), ("keys7", 4), ("keys7", 7)])
+def test_winner_keys_of_wide_tables_by_hand(table, keep):
+    """tables of four and seven columns, keep 3, 4 and 7: distances that arrive ascending, descending and with an equal pair,
+    exactly keep and keep - 1 neighbours taking part, a view named twice"""
+    scene = S.hand_scene_wide()
+    t = hand_terms(scene)
+    codes = R.census(R.reduce_gray(scene["gray"], 1), 1)
+    for (v, i, j), c in scene["codes"].items():
+        assert codes[v, i, j] == c, (v, i, j, hex(int(codes[v, i, j])))
+    nb = S.HAND_NB4 if table == "keys4" else S.HAND_NB7
+    # the tables are what the docstring of the scene says of them
+    assert all(sorted(S.HAND_NB4[r]) == sorted(set(range(C.N_A)) - {r}) for r in range(C.N_A))
+    assert (S.HAND_NB4[C.N_A:] == -1).sum(1).tolist() == [2, 2, 1] and S.HAND_NB4[7].tolist().count(5) == 2
+    assert all(sorted(S.HAND_NB7[r]) == sorted(set(range(8)) - {r}) for r in range(8))
+    keys = R.winners(t, codes, nb, 1, keep, np.flatnonzero(scene["flags"].reshape(-1)))
+    for (r, i, j), want in scene[table][keep].items():
+        assert keys[r, i, j] == want, (r, i, j, hex(int(keys[r, i, j])), hex(int(want)))
+    # the distances of P in the order of the rows of NB4, as the scene states them
+    if table == "keys4" and keep == 4:
+        arrive = [[int(R.popcount(codes[r, 1, 5] ^ codes[n, 1, 5])[0]) for n in S.HAND_NB4[r]] for r in range(C.N_A)]
+        assert arrive == [[1, 3, 6, 8], [7, 1, 5, 2], [3, 2, 3, 5], [6, 5, 3, 2], [8, 7, 5, 2]]
 
 
 def test_agreement_by_hand():
@@ -240,3 +266,118 @@ def test_the_spike_goes_before_the_sphere(sphere):
     print("removed: %.4f of the spike's %d voxels, %.4f of the sphere's own %d voxels"
           % (gone_spike, int(spike.sum()), gone_sphere, int(inside.sum())))
     assert gone_spike > gone_sphere
+
+
+# ------------------------------------------------------------------------------------------------- tables of 3 to 8 columns
+WIDE = [(K, keep) for K in (3, 5, 8) for keep in sorted({1, 3, K - 1, K})]
+# the largest cost of a valid key per keep (the cost of a view grows with the number of distances it adds up): each leaves at
+# least 300 cells valid and some not, which the test asserts of the restatement
+WIDE_MAX_COST = {1: 64, 2: 64, 3: 96, 4: 96, 5: 128, 7: 192, 8: 192}
+
+
+def stages(t, codes, flags, nb, radius, keep, max_cost, m255, min_agree, min_through):
+    """the restatement's four stages on terms and census codes made once"""
+    keys = R.winners(t, codes, nb, radius, keep, np.flatnonzero(np.asarray(flags).reshape(-1) != 0))
+    a = R.agree(t, flags, keys, max_cost, m255)
+    refined, depth = R.refine(t, flags, keys, a, max_cost, m255, min_agree, min_through)
+    return dict(keys=keys, agree=a, refined=refined, depth=depth)
+
+
+@pytest.fixture(scope="module")
+def wide(sphere):
+    """the restatement on the sphere's hull under the tables of S.sphere_table, computed once -> {(K, keep): dict(nb, max_cost,
+    keys, agree, refined, depth)}"""
+    run = sphere[(False, "hull")]
+    out = {}
+    for K, keep in WIDE:
+        nb = S.sphere_table(K, keep)
+        out[(K, keep)] = stages(run["terms"], run["census"], run["flags"], nb, S.SPHERE_RADIUS, keep, WIDE_MAX_COST[keep], M255,
+                                SPHERE["min_agree"], SPHERE["min_through"])
+        out[(K, keep)].update(nb=nb, max_cost=WIDE_MAX_COST[keep])
+    return out
+
+
+def insertion_positions(t, codes, row, r, cand):
+    """int64 [8]: how often a distance of view r's candidates, arriving in the order of its neighbour row, has k of the earlier
+    ones at or below it, k = 0..7 -- the slot of the ascending list it goes to, behind its equals"""
+    codes = np.asarray(codes, np.uint64).reshape(t.V, -1)
+    mine = codes[r][t.cell[r][cand]]
+    earlier, count = [], np.zeros(8, np.int64)
+    for n in row:
+        if n < 0 or n == r:
+            continue
+        d, takes = R.popcount(mine ^ codes[n][t.cell[n][cand]]), t.takes[n][cand]
+        pos = sum(((e_takes & (e_d <= d)).astype(np.int64) for e_d, e_takes in earlier), np.zeros(len(cand), np.int64))
+        count += np.bincount(pos[takes & t.takes[r][cand]], minlength=8)
+        earlier.append((d, takes))
+    return count
+
+
+def wide_conditions(run, w, K, keep):
+    """what the restatement alone says of a table of S.sphere_table and its keys, for the tests on either side: the columns are
+    out of the order of distance, one row has exactly keep entries and one keep - 1, at least 1 000 cells have a key, max_cost
+    leaves at least 300 of them valid and some not; at K = keep = 8 the distances of one view take every slot of the list"""
+    nb = w["nb"]
+    assert nb.shape == (S.SPHERE_V, K) and np.array_equal(np.sort(nb[0]), np.sort(S.sphere_neighbours(K)[0]))
+    assert (nb[3] >= 0).sum() == keep and (nb[8] >= 0).sum() == keep - 1 and ((nb >= 0).sum(1) == K).sum() >= S.SPHERE_V - 2
+    assert any(not np.array_equal(nb[r], S.sphere_neighbours(K)[r]) for r in range(S.SPHERE_V))
+    has = w["keys"] != S.NONE
+    assert has.sum() >= 1000 and not has[8].any() and has[3].any()
+    valid, _ = R.valid_keys(run["terms"], w["keys"], w["max_cost"])
+    assert 300 <= valid.sum() < has.sum()
+    if K == 8 and keep == 8:
+        cand = np.flatnonzero(run["flags"].reshape(-1))[:2000]
+        count = insertion_positions(run["terms"], run["census"], nb[0], 0, cand)
+        print("insertion positions 0..7 of view 0 over %d candidates: %s" % (len(cand), count.tolist()))
+        assert (count > 0).all()
+
+
+@pytest.mark.parametrize("K,keep", WIDE)
+def test_wide_tables_on_the_sphere(sphere, wide, K, keep):
+    wide_conditions(sphere[(False, "hull")], wide[(K, keep)], K, keep)
+
+
+# ------------------------------------------------------------------------------------------------- a view inside the grid
+INSIDE_KEEPS = (2, 3)
+
+
+@pytest.fixture(scope="module")
+def inside():
+    """the sphere's twelve views and the thirteenth inside the grid (S.inside_cameras): the restatement's votes, the hull they
+    give, and the stereo stages on that hull under S.inside_table"""
+    rec = records(S.inside_cameras())
+    gray, mask = S.inside_views()
+    bust = np.full(mask.shape, 255.0, F)
+    pts = CARVE.centres(CARVE.grid_voxels(S.SPHERE_DIMS), S.SPHERE_VMIN, S.SPHERE_VS)
+    votes = CARVE.votes(rec, mask, bust, pts)
+    flags = CARVE.inside_flags(votes).reshape(S.SPHERE_DIMS)
+    t = R.Terms(rec, mask, bust, S.SPHERE_VMIN, S.SPHERE_VS, S.SPHERE_DIMS, S.SPHERE_CELL)
+    codes = R.census(R.reduce_gray(gray, S.SPHERE_CELL), S.SPHERE_RADIUS)
+    nb = S.inside_table()
+    runs = {keep: stages(t, codes, flags, nb, S.SPHERE_RADIUS, keep, SPHERE["max_cost"], M255, SPHERE["min_agree"],
+                         SPHERE["min_through"]) for keep in INSIDE_KEEPS}
+    return dict(records=rec, gray=gray, mask=mask, bust=bust, pts=pts, votes=votes, flags=flags, terms=t, nb=nb, runs=runs)
+
+
+def test_view_inside_the_grid(inside):
+    import oracle
+
+    v = S.INSIDE_VIEW
+    H = W = S.SPHERE_HW
+    batch = np.concatenate([inside["pts"], np.zeros((1, 3), F)])          # (as view_terms projects: not a point alone)
+    _, zp, oob, _ = (a[:-1] for a in oracle.project_points(inside["records"][v], batch, H, W))
+    assert (zp == 0).sum() == 1024 and (zp < 0).sum() == 15360 and (zp > 0).sum() == 16384
+    # behind the view and with an unclamped pixel inside the image: the sign of z' alone makes the view abstain
+    assert ((zp < 0) & ~oob).sum() >= 1000
+    t = inside["terms"]
+    assert not t.seen[v][~(zp > 0)].any() and t.seen[v].sum() == 1496 and np.array_equal(t.seen[v], ~oob & (zp > 0))
+    own = CARVE.votes(inside["records"][v:], inside["mask"][v:], inside["bust"][v:], inside["pts"])
+    assert own[:, 0].sum() == 1496 and np.array_equal(own[:, 0], own[:, 1]) and not own[:, 2].any()
+    # the hull holds candidates on the plane z' = 0, behind the view inside its image, and in front of it
+    f = inside["flags"].reshape(-1) != 0
+    assert (f & (zp == 0)).sum() > 100 and (f & (zp < 0) & ~oob).sum() > 100 and (f & t.takes[v]).sum() > 100
+    nb = inside["nb"]
+    assert nb.shape == (13, 3) and v in nb[0] and v in nb[6] and (nb[v] >= 0).all() and (nb[:v, :2] == S.sphere_neighbours(2)).all()
+    for keep, run in inside["runs"].items():
+        has = run["keys"] != S.NONE
+        assert has[v].sum() > 50 and has[:v].sum() > 1000, keep
